@@ -12,8 +12,11 @@ volumes per GPU, resident in HBM:
   3. U-Net(4->3) forward, DiceLoss, backward, Adam -- DDP over RCCL when N > 1.
 Timing: W warmup steps, then K steps between barrier+synchronize pairs; max over ranks.
 Rank 0 prints one JSON line (see README / task contract), with the dominant filter kernel's
-HBM roofline (HIP events on the launch stream) and a CPU baseline of the reference's filter
-path (the numpy oracle, test infrastructure) on a bounded sample.
+HBM roofline (HIP events on the launch stream, recorded during the timed steps).  ``--full`` adds
+what takes work of its own: a CPU baseline of the reference's filter path (the numpy oracle, test
+infrastructure) on a bounded sample.  ``--dump-outputs DIR`` writes the last timed step's results
+as .npy files (``dump_outputs``); the data, filter draws and network init are seeded, so two runs
+with the same arguments start from identical inputs.
 """
 from __future__ import annotations
 
@@ -33,10 +36,44 @@ for p in (PKG, ROOT):
 # compiled-kernel cache: MIOpen's Find (cudnn.benchmark) then runs once per cache, not once per process
 # and rank (first step 12.9 s cold -> 0.8 s seeded; texbias/__init__ also keeps MIOpen's naive solvers out
 # of Find, which was 140 s).  Set before torch initialises MIOpen; TEXBIAS_MIOPEN_DIR overrides, an
-# existing MIOPEN_* setting wins.
-_MIOPEN_DIR = os.environ.get("TEXBIAS_MIOPEN_DIR", os.path.join(ROOT, "miopen_db"))
-os.environ.setdefault("MIOPEN_USER_DB_PATH", _MIOPEN_DIR)
-os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(_MIOPEN_DIR, "kcache"))
+# existing MIOPEN_* setting wins.  MIOpen rewrites its user db in place, so the process works on a copy of the
+# committed seed (miopen_db/user/, made once; the launcher of a multi-rank run makes it before the ranks start).
+# A tree this user cannot write to is left alone: the copy and the kernel cache then go to the user's cache
+# directory, and where that cannot be written either MIOpen reads the seed in place and keeps nothing.
+_MIOPEN_SEED = os.path.join(ROOT, "miopen_db")
+
+
+def _miopen_dirs():
+    """(user-db directory, kernel-cache directory): the first of miopen_db/ and the user's cache directory
+    that can be written, with the seed's db files copied into its user/ once."""
+    import shutil
+    cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    for base in (_MIOPEN_SEED, os.path.join(cache, "texbias", "miopen_db")):
+        user, kcache = os.path.join(base, "user"), os.path.join(base, "kcache")
+        try:
+            os.makedirs(user, exist_ok=True)
+            os.makedirs(kcache, exist_ok=True)
+            if not (os.access(user, os.W_OK | os.X_OK) and os.access(kcache, os.W_OK | os.X_OK)):
+                continue
+            for name in os.listdir(_MIOPEN_SEED):
+                dst = os.path.join(user, name)
+                if name.endswith("db.txt") and not os.path.exists(dst):
+                    shutil.copyfile(os.path.join(_MIOPEN_SEED, name), f"{dst}.{os.getpid()}")
+                    os.replace(f"{dst}.{os.getpid()}", dst)
+        except OSError:
+            continue
+        return user, kcache
+    return _MIOPEN_SEED, os.path.join(_MIOPEN_SEED, "kcache")
+
+
+if "TEXBIAS_MIOPEN_DIR" in os.environ:
+    _MIOPEN_USER, _MIOPEN_KCACHE = os.environ["TEXBIAS_MIOPEN_DIR"], os.path.join(os.environ["TEXBIAS_MIOPEN_DIR"], "kcache")
+elif "MIOPEN_USER_DB_PATH" in os.environ and "MIOPEN_CUSTOM_CACHE_DIR" in os.environ:
+    _MIOPEN_USER, _MIOPEN_KCACHE = os.environ["MIOPEN_USER_DB_PATH"], os.environ["MIOPEN_CUSTOM_CACHE_DIR"]
+else:
+    _MIOPEN_USER, _MIOPEN_KCACHE = _miopen_dirs()
+os.environ.setdefault("MIOPEN_USER_DB_PATH", _MIOPEN_USER)
+os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", _MIOPEN_KCACHE)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -89,7 +126,19 @@ def parse():
                          "unet: the filter chain still runs eagerly every step (fresh host draws) and writes the "
                          "graph's static input; gibbs-layer: the whole step incl. Gibbs_GD is one graph (the "
                          "layer reads its alpha from device memory)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline of the reference's "
+                         "filter path (cpu_baseline; --no-cpu-baseline still drops it) and, under --graph when the "
+                         "filter launches sit inside the graph, the eager steps that time them after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "the step's return values, the filter chain's output and the model parameters after the "
+                         "step; an array over 16 MB is a fixed seeded sample of its elements (rank 0 only)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps >= 1, --warmup >= 0")
+    if not a.full:
+        a.no_cpu_baseline = True
     c2, c5 = a.config == "c2", a.config == "c5"
     layer = a.model != "unet"
     if layer and a.config != "c3":
@@ -170,6 +219,42 @@ def cpu_baseline(args, shape) -> dict:
             "cpu_model": rep["cpu_model"], "job_cores": rep["job_cores"], "modes": rep["modes"]}
 
 
+DUMP_ARRAY_BYTES = 16 << 20  # per array; no configuration has more than three arrays this large (64 MB in all)
+
+
+def dump_outputs(path: str, returned, filtered, nets: dict) -> None:
+    """``--dump-outputs``: what the last timed step handed back, as float32 ``<name>.npy`` files under ``path``:
+    ``returned_<k>`` (the step's return values: the loss, or the DCGAN step's four scalars; the filter-only
+    configurations return the filtered batch), ``filtered`` (the filter chain's output, the U-Net / DCGAN
+    input, where the step does not return it) and ``params_<net>`` (every parameter of a trained network
+    after the step, flattened and concatenated in ``parameters()`` order).  An array of more than
+    DUMP_ARRAY_BYTES is written as a sample: its flattened elements at sorted indices drawn once from a
+    fixed seed, so two runs with the same arguments sample the same elements."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if torch.is_tensor(returned):
+        returned = (returned,)
+    small = [r for r in (returned or ()) if torch.is_tensor(r)]
+    if len(small) == 1 and small[0] is filtered:
+        filtered = None  # written once, as returned_0
+    for k, r in enumerate(small):
+        arrays[f"returned_{k}"] = r.detach().reshape(-1)
+    if filtered is not None:
+        arrays["filtered"] = filtered.detach().reshape(-1)
+    for name, net in nets.items():
+        arrays[f"params_{name}"] = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+    keep = DUMP_ARRAY_BYTES // 4
+    for name, a in arrays.items():
+        if a.numel() > keep:
+            g = torch.Generator().manual_seed(20240607)
+            idx = torch.randint(0, a.numel(), (keep,), generator=g).sort().values
+            arrays[name] = a[idx.to(a.device)]
+    if sum(4 * a.numel() for a in arrays.values()) > 64 << 20:
+        raise SystemExit("--dump-outputs: more than 64 MB to write")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a.float().cpu().numpy())
+
+
 def main():
     args = parse()
     maybe_launch_ranks(args)
@@ -233,11 +318,13 @@ def main():
         sap.p = float(prs.uniform(0.05, 0.35))
 
     step_fn = None
+    nets = {}  # --dump-outputs: the networks the step trains, by name
     if args.config == "c5":
         from texbias.dcgan import DCGANStep
         torch.backends.cudnn.benchmark = not args.no_cudnn_benchmark
         torch.manual_seed(0)  # identical network init on every rank
         step_fn = DCGANStep(dev, distributed=world > 1, bf16=not args.fp32, channels_last=args.channels_last)
+        nets = {"G": step_fn.G, "D": step_fn.D}
         torch.manual_seed(1000 + rank)
     elif layer_model:
         import stylization_layers as SL
@@ -253,6 +340,7 @@ def main():
         step_fn = TrainStep(lm, dev, distributed=world > 1, bucket_cap_mb=args.bucket_mb, capturable=args.graph)
         gd = gibbs_gd if args.model == "gibbs-layer" else spike_gd
         train_step = step_fn
+        nets = {"model": train_step.module}
 
         def step_fn(x, y):  # noqa: F811 - train step, then the layer's finite-difference update
             loss = train_step(x, y)
@@ -262,6 +350,9 @@ def main():
         torch.backends.cudnn.benchmark = not args.no_cudnn_benchmark
         step_fn = TrainStep(reference_model(C, 3), dev, distributed=world > 1, bucket_cap_mb=args.bucket_mb,
                             channels_last=args.channels_last, capturable=args.graph)
+        nets = {"model": step_fn.module}
+
+    kept = {}  # --dump-outputs: the last step's filter-chain output (a reference, no copy)
 
     def one_step(i):
         if args.random_filters:
@@ -269,6 +360,8 @@ def main():
         if layer_model:  # the filter is the model's first layer
             return step_fn(pool[i % 2], labels[i % 2])
         y = chain(pool[i % 2], pad=pad)
+        if args.dump_outputs:
+            kept["filtered"] = y
         if args.config == "c5":
             return step_fn(y.view(B, 1, W, D))
         if step_fn is not None:
@@ -300,17 +393,20 @@ def main():
                 if rank == 0:
                     print(f"[bench] warmup step {i}: {time.perf_counter() - t_w:.3f} s", file=sys.stderr, flush=True)
         torch.cuda.current_stream(dev).wait_stream(side)
-        graphs = []
+        graphs, graph_out = [], []
         for k in range(2):  # one graph per resident batch; one memory pool, replayed in capture order
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
-                body(k)
+                graph_out.append(body(k))  # the step's static return values, rewritten by every replay
             graphs.append(g)
         torch.cuda.synchronize(dev)
+        if xs is not None:
+            kept["filtered"] = xs
 
         def one_step(i):  # noqa: F811
             fill(i)
             graphs[i % 2].replay()
+            return graph_out[i % 2]
     else:
         for i in range(args.warmup):
             t_w = time.perf_counter()
@@ -334,8 +430,10 @@ def main():
     elapsed = time.perf_counter() - t0
     ms, cnt, nbytes, kernels = rt.pass_stats()
     rt.set_pass_timing(False)
+    if args.dump_outputs and rank == 0:  # before anything else runs on the model: the last timed step's results
+        dump_outputs(args.dump_outputs, last, kept.get("filtered"), nets)
     stat_steps = args.steps
-    if graphs is not None and not any(cnt[:3]):
+    if args.full and graphs is not None and not any(cnt[:3]):
         # the filter launches sit inside the graph: time them on eager steps after the timed region
         stat_steps = min(args.steps, 5)
         rt.set_pass_timing(True)
@@ -363,9 +461,9 @@ def main():
                     passes[nm]["algorithmic_MB"] = round(per_launch / 1e6, 2)
                     passes[nm]["GB_s"] = round(per_launch / (avg * 1e-3) / 1e9, 1)
         # the dominant (longest) k-space pass, its bytes and time both measured live on its stream
-        dom = max((n for n in names[:3] if n in passes and "GB_s" in passes[n]), key=lambda n: passes[n]["avg_ms"])
-        ach = passes[dom]["GB_s"]
-        dom_bytes = passes[dom]["algorithmic_bytes"]
+        # (none without --full when the filter launches sit inside a replayed graph: no events were recorded)
+        timed = [n for n in names[:3] if n in passes and "GB_s" in passes[n]]
+        dom = max(timed, key=lambda n: passes[n]["avg_ms"]) if timed else None
         if layer_model:
             workload = f"LAYER DRIVER {args.model}: " + (
                 "Gibbs_UNet(1->1) with GibbsNoiseLayer alpha 0.7 (device-resident), train step + Gibbs_GD "
@@ -383,8 +481,17 @@ def main():
                         + (" [train step replayed as a HIP graph]" if args.graph else ""))
         else:
             workload = "C2 Gibbs truncation: RandFourierDiskMaskd(r=12.5) low-pass alone, batched 4x128^3 volumes"
-        traffic, traffic_file = pmc_traffic(passes[dom]["kernel"], dom_bytes,
-                                            args.chain if args.config == "c3" and args.chain != "ref" else args.config)
+        roofline = None
+        if dom is not None:
+            ach = passes[dom]["GB_s"]
+            dom_bytes = passes[dom]["algorithmic_bytes"]
+            traffic, traffic_file = pmc_traffic(passes[dom]["kernel"], dom_bytes,
+                                                args.chain if args.config == "c3" and args.chain != "ref" else args.config)
+            roofline = {"kernel": passes[dom]["kernel"], "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                        "traffic": traffic,
+                        "traffic_unit": f"bytes per launch (rocprofv3 PMC, {traffic_file})",
+                        "algorithmic_bytes_per_launch": dom_bytes}
         line = {
             "metric": METRIC,
             "value": round(vols / elapsed, 4),
@@ -406,11 +513,7 @@ def main():
                 "global_batch": B * world,
                 "parallelism": f"dp{world}",
             },
-            "roofline": {"kernel": passes[dom]["kernel"], "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                         "traffic": traffic,
-                         "traffic_unit": f"bytes per launch (rocprofv3 PMC, {traffic_file})",
-                         "algorithmic_bytes_per_launch": dom_bytes},
+            "roofline": roofline,
             "filter_passes": passes,
             "filter_ms_per_step": round(sum(ms) / stat_steps, 4),
         }
