@@ -336,6 +336,43 @@ int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, co
 int tb_conv3d_gemm_config(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride, int ksize, int64_t* cfg);
 
 /*
+ * The weight gradient of the U-Net's deepest levels as one implicit GEMM on the f32 matrix cores
+ * (csrc/conv_wgrad_gemm.hip; train step of 10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-243, MONAI
+ * UNet module tree source_code/test.ipynb:754-1010 -- the 15 x 15 x 10 level at the C3 shape: the stride-2
+ * entry 64 -> 128 with its residual, 128 -> 128, the bottom unit 128 -> 256 / 256 -> 256 with its 1x1x1
+ * residual, ConvTranspose3d 384 -> 64 -- whose short rows leave tb_conv3d_wgrad_f32's z-march nothing to
+ * march over and which MIOpen ran as im2col + GEMM or CK between layout transposes):
+ *   dW[m][c][t] = sum_{n, o} G[n][m][o] X[n][c][stride o + tap_t - pad]      (zero outside X)
+ * the contract of tb_conv3d_wgrad_f32, for ksize 3 (pad 1, stride 1 or 2) or ksize 1 (pad 0, stride 1).
+ * G [N][M][Do][Ho][Wo] with batch stride gsn floats (0: contiguous), X [N][C][Di][Hi][Wi] with batch
+ * stride xsn (0: contiguous) -- a channel slice of a wider buffer is read in place; dW [M][C][ksize^3]
+ * contiguous.  A ConvTranspose3d(stride 2, padding 1, output_padding 1) passes G = the layer's input and
+ * X = the output gradient, so dW is [Cin][Cout][27] as the module holds it.  Any 4-byte aligned pointers.
+ * The reduction is split into slices of whole 32-position stages that never straddle a sample; partial tiles
+ * go to ws (tb_conv3d_wgrad_gemm_ws_bytes(...) bytes, stream-ordered reuse) and one reduction sums them in
+ * slice order: deterministic, no float atomics, no host sync, no allocation (graph-capturable).
+ * tb_conv3d_wgrad_gemm_ws_bytes returns 0 when no plan exists for the shape (an operand of 2^29 floats or
+ * more, 2^21 positions per sample or more); tb_conv3d_wgrad_gemm_f32 then returns TB_ERR_UNSUPPORTED_SIZE /
+ * TB_ERR_INVALID_ARG and launches nothing.  tb_conv3d_wgrad_gemm_config (host only): cfg[0..4] = BM, BP,
+ * slices (nsplit), positions per slice (kper), blocks.  The _ex forms take the slices per sample
+ * (sps > 0; 0: planned) for tests and measurement scripts.
+ */
+size_t tb_conv3d_wgrad_gemm_ws_bytes(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                     int ksize);
+int tb_conv3d_wgrad_gemm_f32(const float* G, int64_t gsn, const float* X, int64_t xsn, float* dW, int N, int M, int C,
+                             int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int ksize, void* ws,
+                             size_t ws_bytes, void* stream);
+int tb_conv3d_wgrad_gemm_config(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                int ksize, int64_t* cfg);
+size_t tb_conv3d_wgrad_gemm_ws_bytes_ex(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                        int ksize, int sps);
+int tb_conv3d_wgrad_gemm_ex_f32(const float* G, int64_t gsn, const float* X, int64_t xsn, float* dW, int N, int M, int C,
+                                int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int ksize, int sps, void* ws,
+                                size_t ws_bytes, void* stream);
+int tb_conv3d_wgrad_gemm_config_ex(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                   int ksize, int sps, int64_t* cfg);
+
+/*
  * Fused InstanceNorm3d(affine=False, eps) + PReLU(one weight a) over NC instances of S contiguous
  * voxels (x as [N][C][D][H][W], NC = N*C) -- the "ADN" block after every U-Net convolution
  * (MONAI Convolution, used by 10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-199).

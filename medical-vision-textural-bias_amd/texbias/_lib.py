@@ -70,6 +70,12 @@ def _proto(L):
         "tb_conv3d_gemm_workspace_bytes": (SZ, [I] * 9),
         "tb_conv3d_gemm_f32": (I, [I, P, I64, P, P, P, I64, P, I64] + [I] * 8 + [P, SZ, P]),
         "tb_conv3d_gemm_config": (I, [I] * 9 + [P]),
+        "tb_conv3d_wgrad_gemm_ws_bytes": (SZ, [I] * 11),
+        "tb_conv3d_wgrad_gemm_f32": (I, [P, I64, P, I64, P] + [I] * 11 + [P, SZ, P]),
+        "tb_conv3d_wgrad_gemm_config": (I, [I] * 11 + [P]),
+        "tb_conv3d_wgrad_gemm_ws_bytes_ex": (SZ, [I] * 12),
+        "tb_conv3d_wgrad_gemm_ex_f32": (I, [P, I64, P, I64, P] + [I] * 12 + [P, SZ, P]),
+        "tb_conv3d_wgrad_gemm_config_ex": (I, [I] * 12 + [P]),
         "tb_dice_sums_f32": (I, [P, P, P, I64, I64, I, I, P]),
         "tb_dice_sums_ws_bytes": (SZ, [I64, I64]),
         "tb_dice_sums_ws_f32": (I, [P, P, P, I64, I64, I, I, P, SZ, P]),

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import check, lib
+from ._lib import TexbiasError, check, lib
 
 # use the custom weight gradient when the reduction is long relative to the output tile;
 # TEXBIAS_WGRAD=0 leaves every layer to MIOpen (e.g. to compare with MIOpen's Find choice)
@@ -140,12 +140,108 @@ def fast_wgrad_applies(x: torch.Tensor, w: torch.Tensor, out_spatial, stride, pa
     # the z-marching kernels (partial tiles, no atomics) take any reduction length; the general split-K
     # kernel only long ones
     if ZMARCH_MIN_POS and pos_of(x, out_spatial, transposed) >= ZMARCH_MIN_POS and \
-            _wgrad_ws_bytes(*g_shape[:2], x_shape[1], *g_shape[2:], *x_shape[2:], s, 1) > 0:
+            _wgrad_ws_bytes(*g_shape[:2], x_shape[1], *g_shape[2:], *x_shape[2:], s, 1) > 0 and \
+            _wgrad_tiles(g_shape, x_shape, s):
+        # (the workspace query assumes 16-B aligned operands; a misaligned call falls back to the atomic
+        # split-K kernel inside the library, which needs a tiling of its own)
         return True
     pos = x.shape[0] * math.prod(out_spatial if not transposed else x.shape[2:])
     if pos < MIN_K_PER_OUTPUT * w.shape[0] * w.shape[1] * 27 // 16:
         return False
     return _wgrad_tiles(g_shape, x_shape, s)
+
+
+# ---------------------------------------------------------------- deep-level weight gradients as a GEMM
+# Weight gradients on k_conv_wgrad_gemm (csrc/conv_wgrad_gemm.hip) instead of MIOpen's im2col + GEMM / CK
+# between layout transposes; False leaves every layer on its earlier route (z-march or ATen).
+WGRAD_GEMM = True
+# The gate is a shape class, from profiles/r7/conv/wgrad_gemm_vs_miopen.txt (us per call, caches flushed, batch 2):
+#   * positions per sample (Do Ho Wo of G) at most WGRAD_GEMM_MAX_POS: at 15 x 15 x 10 = 2250 the kernel wins
+#     every layer (73-183 us against MIOpen's 96-250); at 30 x 30 x 20 = 18000 the z-march kernels hold the
+#     layers (99-125 us against 136-210 here);
+#   * and at least WGRAD_GEMM_MIN_POS: at the 128 x 128 x 64 crop's 8 x 8 x 4 = 256 the calls are launch-sized
+#     (26-39 us against 32-53, two layers level) and the crop step showed no clear gain (graph replay 4.92 ->
+#     4.88 ms, under three spreads; eager 5.02 -> 5.41 ms in a host-bound, noisy measurement;
+#     profiles/r7/ab/crop.jsonl), so those layers stay on MIOpen;
+#   * channel product M C at least WGRAD_GEMM_MIN_MC: below it (32 x 128 at 16 x 16 x 8: 62 us against 41) the
+#     64- / 128-wide tiles are too few to fill the chip.
+# Nothing was measured between the bounds and the nearest shapes on either side of them.
+WGRAD_GEMM_MIN_POS = 1024
+WGRAD_GEMM_MAX_POS = 4608
+WGRAD_GEMM_MIN_MC = 8192
+
+
+def _wgg_geom(G: torch.Tensor, X: torch.Tensor, stride: int, ksize: int, sps: int = 0):
+    return (G.shape[0], G.shape[1], X.shape[1], *G.shape[2:], *X.shape[2:], stride, ksize, sps)
+
+
+@functools.lru_cache(maxsize=256)
+def _wgg_ws_bytes(*geom) -> int:
+    return int(lib().tb_conv3d_wgrad_gemm_ws_bytes_ex(*geom))
+
+
+def wgrad_gemm_config(g_shape, x_shape, stride: int, ksize: int = 3, sps: int = 0):
+    """The tiling ``wgrad_gemm`` picks for G [N, M, Do, Ho, Wo] / X [N, C, Di, Hi, Wi] (host only,
+    tb_conv3d_wgrad_gemm_config): BM, BP, nsplit, kper, blocks -- or None when no plan exists."""
+    import ctypes
+    cfg = (ctypes.c_int64 * 5)()
+    if lib().tb_conv3d_wgrad_gemm_config_ex(g_shape[0], g_shape[1], x_shape[1], *g_shape[2:], *x_shape[2:], stride,
+                                            ksize, sps, cfg) != 0:
+        return None
+    return dict(zip(("BM", "BP", "nsplit", "kper", "blocks"), list(cfg)))
+
+
+def _chan_plain(t: torch.Tensor) -> torch.Tensor:
+    """[N, C, D, H, W] with contiguous channels (any batch stride: a channel slice is read in place)."""
+    sp = math.prod(t.shape[2:])
+    if t.stride(4) == 1 and t.stride(3) == t.shape[4] and t.stride(2) == t.shape[3] * t.shape[4] and \
+            t.stride(1) == sp and (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * sp):
+        return t
+    return t.contiguous()
+
+
+def wgrad_gemm(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, ksize: int = 3, sps: int = 0) -> torch.Tensor:
+    """dW[m][c][k^3] = sum_{n, o} G[n][m][o] X[n][c][stride o + tap - pad] on the implicit-GEMM kernel
+    (tb_conv3d_wgrad_gemm_f32, include/texbias.h): ksize 3 (padding 1, stride 1 / 2) or 1 (padding 0);
+    a ConvTranspose3d passes G = its input, X = the output gradient.  ``sps`` > 0 forces the slices per
+    sample of the reduction split (tests, measurement scripts)."""
+    G, X = _chan_plain(G), _chan_plain(X)
+    geom = _wgg_geom(G, X, stride, ksize, sps)
+    nb = _wgg_ws_bytes(*geom)
+    if nb == 0:
+        raise TexbiasError("tb_conv3d_wgrad_gemm_f32: no plan for this shape")
+    N, M, Cc = geom[:3]
+    dW = torch.empty((M, Cc) + (ksize,) * 3, dtype=torch.float32, device=G.device)
+    ws = torch.empty(nb, dtype=torch.uint8, device=G.device)
+    with torch.cuda.device(G.device):
+        check(lib().tb_conv3d_wgrad_gemm_ex_f32(G.data_ptr(), G.stride(0) if N > 1 else 0, X.data_ptr(),
+                                                X.stride(0) if N > 1 else 0, dW.data_ptr(), *geom, ws.data_ptr(), nb,
+                                                _stream(G)), "tb_conv3d_wgrad_gemm_f32")
+    return dW.view(w_shape)
+
+
+def wgrad_gemm_applies(x: torch.Tensor, w: torch.Tensor, out_spatial, stride, padding, transposed: bool,
+                       output_padding=(0, 0, 0)) -> bool:
+    """The layer's weight gradient goes to ``wgrad_gemm``: 3x3x3 (padding 1, stride 1 / 2; transposed: stride 2,
+    output_padding 1) or 1x1x1 (padding 0, stride 1) in the shape class of WGRAD_GEMM_MIN_POS /
+    WGRAD_GEMM_MAX_POS / WGRAD_GEMM_MIN_MC, and the library has a plan for it."""
+    if not (WGRAD_GEMM and custom_backward_applies(x, w) and x.dim() == 5 and len(set(stride)) == 1 and
+            len(set(padding)) == 1 and len(set(w.shape[2:])) == 1):
+        return False
+    k, s, p = w.shape[2], stride[0], padding[0]
+    if not ((k == 3 and p == 1 and s in (1, 2)) or (k == 1 and p == 0 and s == 1 and not transposed)):
+        return False
+    if transposed:  # G = x, X = the output gradient
+        if s != 2 or tuple(output_padding) != (1, 1, 1):
+            return False
+        g_shape = tuple(x.shape)
+        x_shape = (x.shape[0], w.shape[1]) + tuple(2 * n for n in x.shape[2:])
+    else:
+        g_shape, x_shape = (x.shape[0], w.shape[0]) + tuple(out_spatial), tuple(x.shape)
+    if not WGRAD_GEMM_MIN_POS <= math.prod(g_shape[2:]) <= WGRAD_GEMM_MAX_POS or \
+            g_shape[1] * x_shape[1] < WGRAD_GEMM_MIN_MC:
+        return False
+    return _wgg_ws_bytes(g_shape[0], g_shape[1], x_shape[1], *g_shape[2:], *x_shape[2:], s, k, 0) > 0
 
 
 GEMM = os.environ.get("TEXBIAS_CONVGEMM", "1") != "0"
@@ -470,7 +566,7 @@ class Route:
     ``mfma`` (k_conv3d_mfma_s1), ``fewin`` (k_conv_s2_fewin), ``small`` (k_conv3d_small_z), ``fewout``
     (k_convT_fewout), ``convT64`` (k_convT_mfma64), ``gemm`` (k_conv_gemm), ``aten`` (MIOpen / CK)."""
 
-    __slots__ = ("kind", "dx", "stride", "padding", "output_padding", "transposed", "fast_w", "k")
+    __slots__ = ("kind", "dx", "stride", "padding", "output_padding", "transposed", "fast_w", "k", "wgg")
 
     def __init__(self, x: torch.Tensor, w: torch.Tensor, stride, padding, output_padding, transposed: bool):
         self.stride, self.padding = tuple(stride), tuple(padding)
@@ -505,14 +601,18 @@ class Route:
                 # ConvTranspose3d: a stride-2 Conv3d of dY (the GEMM's conv form); stride-1 Conv3d: the
                 # flipped-weight form; stride-2 Conv3d: the sub-pixel form (GEMM_T)
                 self.dx = "gemm"
-        # weight gradient: the texbias MFMA kernels where a tiling exists and the reduction is long
-        if self.kind in ("fwd16", "mfma", "fewin", "small", "fewout"):
+        # weight gradient: the deep levels' GEMM form first, else the texbias MFMA kernels where a tiling
+        # exists and the reduction is long
+        osp = None if transposed else [(n + 2 * p - kk) // s + 1
+                                      for n, p, s, kk in zip(x.shape[2:], pd, st, w.shape[2:])]
+        self.wgg = wgrad_gemm_applies(x, w, osp, st, pd, transposed, op)
+        if self.wgg:
+            self.fast_w = True
+        elif self.kind in ("fwd16", "mfma", "fewin", "small", "fewout"):
             self.fast_w = True
         elif self.kind == "aten" and not custom_backward_applies(x, w):
             self.fast_w = False
         else:
-            osp = None if transposed else [(n + 2 * p - kk) // s + 1
-                                          for n, p, s, kk in zip(x.shape[2:], pd, st, w.shape[2:])]
             self.fast_w = fast_wgrad_applies(x, w, osp, st, pd, transposed, op)
 
     # -- forward (``add``: summed into the output -- in the kernel's store where the kernel takes it)
@@ -577,6 +677,9 @@ class Route:
 
     # -- weight gradient
     def weight_grad(self, gy, x, w):
+        if self.wgg:
+            G, X = (x, gy) if self.transposed else (gy, x)
+            return wgrad_gemm(G, X, w.shape, self.stride[0], self.k)
         if self.fast_w and tuple(w.shape[2:]) == (3, 3, 3) and self.padding[0] == 1:
             return weight_grad(gy, x, w, self.stride[0], self.transposed, self.output_padding)
         _, gw, _ = torch.ops.aten.convolution_backward(
