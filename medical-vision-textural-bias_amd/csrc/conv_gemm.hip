@@ -22,32 +22,23 @@
 //
 // k runs tap-major (k = tap Cin + c, A packed to match by k_cg_pack; Cin % 8 == 0), so the 8 k rows a
 // wave gathers per stage are 8 channels of ONE tap: the tap's offset and every lane's validity bit are
-// per stage, the 8 loads per lane one base address plus channel strides.  Tiling: a 256-thread block
-// computes a BM x BP tile of Y over k stages of 32: A rows staged by float4 loads, X~ gathered by scalar
-// loads (each lane's positions fixed for the block), both stored to LDS as [row][k parity][16 steps]
-// so that each lane reads its 16 operands of a stage as four 16-B reads.  The waves (WGM x 4/WGM) own TM x TN tiles
-// of 32 x 32 on mfma_f32_32x32x2f32 (exact f32: one rounding per product, as a k-ordered fmaf chain).
-// Stages are double-buffered (the next stage's global loads in registers while the current one runs
-// from LDS; one barrier per stage).  Small GEMMs split k over nsplit slices into float partials summed
-// by k_cg_reduce (which adds bias / add and scatters to the output grid).  Blocks are numbered so that
-// the m tiles of one position tile land on one XCD (its L2 serves the X~ re-reads).
+// per stage, the 8 loads per lane one base address plus channel strides.  A block computes a BM x BP tile
+// of Y on the tile pipeline of gemm_core.h: A rows staged by float4 loads, X~ gathered by scalar loads
+// (each lane's positions fixed for the block).  Small GEMMs split k over nsplit slices into float
+// partials summed by k_cg_reduce (which adds bias / add and scatters to the output grid).  Blocks are
+// numbered so that the m tiles of one position tile land on one XCD (its L2 serves the X~ re-reads).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
-#include <mutex>
-#include <type_traits>
 
+#include "gemm_core.h"
+#include "num_cu.h"
 #include "texbias.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int KC = 32;    // k rows per stage
-constexpr int NTH = 256;  // threads per block
-constexpr int RS = 36;    // LDS floats per tile row: 32 k + 4 pad (16-B reads of 16 rows hit distinct banks)
+using namespace tb::gemm;
 
 struct CGArgs {
   const float* x;
@@ -88,21 +79,13 @@ __host__ __device__ inline void tap_of(int kind, int cls, int j, int& dz, int& d
   }
 }
 
-__device__ __forceinline__ int xcd_remap(int b, int nb) {
-  // hardware dispatch sends block b to XCD b % 8: give XCD x the contiguous logical range of blocks
-  const int q = nb >> 3, r = nb & 7, x = b & 7, i = b >> 3;
-  return x < r ? x * (q + 1) + i : r * (q + 1) + (x - r) * q + i;
-}
-
 template <int BM, int BP, int WGM>
 __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
-  constexpr int WGN = 4 / WGM;
-  constexpr int TM = BM / WGM / 32, TN = BP / WGN / 32;
+  using TileT = Tile<BM, BP, WGM>;
   constexpr int NPOS = BP / 64;          // gather positions per lane
   constexpr int AQ = BM * KC / 4 / NTH;  // A float4 per thread per stage
-  static_assert(TM >= 1 && TN >= 1 && NPOS >= 1 && AQ >= 1, "tile");
+  static_assert(NPOS >= 1 && AQ >= 1, "tile");
   extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
-  constexpr int LBUF = (BM + BP) * RS;   // floats per stage buffer
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int b = xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -111,7 +94,7 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
   const int pt = b % a.ptiles;
   b /= a.ptiles;
   const int split = b % a.nsplit, cls = b / a.nsplit;
-  const int T = a.Tc[cls], K = a.Kc[cls], Kld = K;
+  const int T = a.Tc[cls], K = a.Kc[cls];
   const float* __restrict__ A = a.A + a.aoff[cls];
   const int Cin = a.Cin;
   const int k_beg = split * a.kper;
@@ -151,9 +134,7 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)xbytes, 0x00020000);
   const int xsc4 = 4 * a.xsc;
 
-  // two register slots: the loads of stage s + 2 are in flight while stage s runs from LDS and stage
-  // s + 1 (loaded one stage earlier) is written to the other LDS buffer.  LDS rows hold k in natural
-  // order; the MFMA step st pairs k = st (lanes 0-31) with k = 16 + st (lanes 32-63).
+  // the stagers' two register slots (gemm_core.h); stage s holds k rows k_beg + 32 s .. + 31
   float rb[2][NPOS][8];
   f32x4 ra[2][AQ];
   auto gather = [&](auto SL, int k0) {
@@ -175,7 +156,7 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
         rb[sl][i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, vo, soff + r * xsc4, 0));
     }
   };
-  const uint32_t abytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(4 * (int64_t)a.M * Kld));
+  const uint32_t abytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(4 * (int64_t)a.M * K));
   const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)abytes, 0x00020000);
   auto aload = [&](auto SL, int k0) {
     constexpr int sl = decltype(SL)::value;
@@ -183,13 +164,17 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
     for (int u = 0; u < AQ; ++u) {
       const int q4 = tid + NTH * u, row = q4 % BM, kq = k0 + 4 * (q4 / BM);
       const int m = m0 + row;
-      const int vo = (m < a.M && kq < k_end) ? 4 * (m * Kld + kq) : (int)0x80000000;
+      const int vo = (m < a.M && kq < k_end) ? 4 * (m * K + kq) : (int)0x80000000;
       ra[sl][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ar, vo, 0, 0));
     }
   };
-  auto stage_store = [&](auto SL) {  // slot sl -> LDS buffer sl (stage s uses slot and buffer s & 1)
+  auto load = [&](auto SL, int s) {  // masked by k < k_end: past the slice both read zeros
+    gather(SL, k_beg + s * KC);
+    aload(SL, k_beg + s * KC);
+  };
+  auto store = [&](auto SL) {
     constexpr int sl = decltype(SL)::value;
-    float* L = lds_dyn + sl * LBUF;
+    float* L = lds_dyn + sl * TileT::LBUF;
 #pragma unroll
     for (int u = 0; u < AQ; ++u) {
       const int q4 = tid + NTH * u, row = q4 % BM, c4 = q4 / BM;
@@ -203,85 +188,26 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
     }
   };
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  TileT tile(w, lane);
+  // an empty slice (a sub-pixel class whose K ends before k_beg) runs no stage and stores zeros
+  tile.run(lds_dyn, k_beg < k_end ? (k_end - k_beg + KC - 1) / KC : 0, load, store);
 
-  const int wm = w % WGM, wn = w / WGM;
-  const int kk = lane >> 5, l32 = lane & 31;
-  // steps h*8 .. h*8+7 of the stage in LDS buffer sl
-  auto compute_half = [&](auto SL, auto H) {
-    constexpr int sl = decltype(SL)::value, h = decltype(H)::value;
-    const float* L = lds_dyn + sl * LBUF;
-    f32x4 af[TM][2], bf[TN][2];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const float* src = L + ((wm * TM + tm) * 32 + l32) * RS + 16 * kk + 8 * h;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) af[tm][q] = *reinterpret_cast<const f32x4*>(src + 4 * q);
-    }
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      const float* src = L + (BM + (wn * TN + tn) * 32 + l32) * RS + 16 * kk + 8 * h;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) bf[tn][q] = *reinterpret_cast<const f32x4*>(src + 4 * q);
-    }
-#pragma unroll
-    for (int st = 0; st < 8; ++st)
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tm][st >> 2][st & 3], bf[tn][st >> 2][st & 3],
-                                                             acc[tm][tn], 0, 0, 0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  const int nst = k_beg < k_end ? (k_end - k_beg + KC - 1) / KC : 0;
-  if (nst > 0) {
-    gather(I0{}, k_beg);
-    aload(I0{}, k_beg);
-    stage_store(I0{});
-    gather(I1{}, k_beg + KC);
-    aload(I1{}, k_beg + KC);
+  const int M = a.M, P = a.P;
+  if (a.nsplit > 1) {
+    tile.epilogue([&](int col) {
+      const int p = p0 + col;
+      float* dst = a.part + ((int64_t)(cls * a.nsplit + split) * M) * P + p;
+      return [=](int row, float v) {
+        const int m = m0 + row;
+        if (p < P && m < M) dst[(int64_t)m * P] = v;
+      };
+    });
+    return;
   }
-  __syncthreads();
-  // stage s: its first 8 MFMA steps, then the loads of stage s + 2 (past the end they read zeros through
-  // the descriptors' range check: no branches), the last 8 steps, stage s + 1 to the other LDS buffer
-  auto body = [&](auto SL, int s) {
-    using O = std::integral_constant<int, 1 - decltype(SL)::value>;
-    compute_half(SL, I0{});
-    gather(SL, k_beg + (s + 2) * KC);
-    aload(SL, k_beg + (s + 2) * KC);
-    compute_half(SL, I1{});
-    stage_store(O{});
-    __syncthreads();
-  };
-  for (int s = 0; s < nst; s += 2) {
-    body(I0{}, s);
-    if (s + 1 < nst) body(I1{}, s + 1);
-  }
-
-  // epilogue: C column = position (lane & 31), rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int p = p0 + (wn * TN + tn) * 32 + l32;
-    if (p >= a.P) continue;
-    if (a.nsplit > 1) {
-      float* dst = a.part + ((int64_t)(cls * a.nsplit + split) * a.M) * a.P + p;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-          if (m < a.M) dst[(int64_t)m * a.P] = acc[tm][tn][r];
-        }
-      continue;
-    }
+  const float* bias = a.bias;
+  const int ysc = a.ysc;
+  tile.epilogue([&](int col) {
+    const int p = p0 + col;
     int t = p;
     const int ox = t % a.OW;
     t /= a.OW;
@@ -293,18 +219,15 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
                        a.ymul * ox + (pc & 1);
     float* yo = a.y + n * a.ysn + sp;
     const float* ad = a.add ? a.add + n * a.addsn + sp : nullptr;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-        if (m < a.M) {
-          float v = acc[tm][tn][r] + (a.bias ? a.bias[m] : 0.f);
-          if (ad) v += ad[(int64_t)m * a.ysc];
-          yo[(int64_t)m * a.ysc] = v;
-        }
+    return [=](int row, float v) {
+      const int m = m0 + row;
+      if (p < P && m < M) {
+        v += bias ? bias[m] : 0.f;
+        if (ad) v += ad[(int64_t)m * ysc];
+        yo[(int64_t)m * ysc] = v;
       }
-  }
+    };
+  });
 }
 
 // y = bias + add + sum of the split partials, scattered to the output grid; one thread per (cls, m, q)
@@ -343,30 +266,17 @@ __global__ __launch_bounds__(256) void k_cg_pack(const float* __restrict__ W, fl
   int cls = 0;
   while (cls + 1 < a.ncls && i >= a.aoff[cls + 1]) ++cls;
   const int64_t r = i - a.aoff[cls];
-  const int Kc = a.Kc[cls], T = a.Tc[cls], Cin = a.Cin, M = a.M;
+  const int Kc = a.Kc[cls], Cin = a.Cin, M = a.M;
   const int m = (int)(r / Kc), k = (int)(r - (int64_t)m * Kc);
   const int j = k / Cin, c = k - j * Cin;
   int dz, dy, dx, wi;
   tap_of(a.kind, cls, j, dz, dy, dx, wi);
   const int TW = a.kind == 1 ? 1 : 27;  // taps in the weight tensor
-  (void)T;
   float v;
   if (mode == 0) v = W[((int64_t)m * Cin + c) * TW + wi];
   else if (mode == 1) v = W[((int64_t)c * M + m) * TW + (TW - 1 - wi)];
   else v = W[((int64_t)c * M + m) * 27 + wi];
   out[i] = v;
-}
-
-int g_ncu = 0;
-int num_cu() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&g_ncu, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess)
-      g_ncu = 256;
-  });
-  return g_ncu > 0 ? g_ncu : 256;
 }
 
 struct Plan {
@@ -376,7 +286,6 @@ struct Plan {
 };
 
 inline size_t align_floats(size_t n) { return (n + 63) & ~size_t(63); }
-inline size_t lds_bytes(int BM, int BP) { return (size_t)2 * (BM + BP) * RS * sizeof(float); }
 
 // Fill the geometry and tiling of a call (no device pointers).  Returns TB_OK or an error code.
 int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride, int ksize, Plan& pl) {
@@ -413,8 +322,8 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
   if ((int64_t)N * M * a.ysc >= (int64_t)1 << 31) return TB_ERR_UNSUPPORTED_SIZE;
   a.P = N * a.OD * a.OH * a.OW;
   // tile: M <= 32 -> 32 x 128; M <= 64 -> 64 x 64; else 128 x 128
-  const int tile = M <= 32 ? 1 : (M <= 64 ? 2 : 5);
-  static const int cfg[6][3] = {{0, 0, 0}, {32, 128, 1}, {64, 64, 2}, {128, 64, 2}, {64, 128, 2}, {128, 128, 2}};
+  static const int cfg[3][3] = {{32, 128, 1}, {64, 64, 2}, {128, 128, 2}};
+  const int tile = M <= 32 ? 0 : (M <= 64 ? 1 : 2);
   pl.BM = cfg[tile][0], pl.BP = cfg[tile][1], pl.WGM = cfg[tile][2];
   a.mtiles = (M + pl.BM - 1) / pl.BM;
   a.ptiles = (a.P + pl.BP - 1) / pl.BP;
@@ -425,7 +334,7 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
   const int64_t base = (int64_t)a.mtiles * a.ptiles * a.ncls;
   int occ = (int)(163840 / lds_bytes(pl.BM, pl.BP));
   occ = occ > 4 ? 4 : (occ < 1 ? 1 : occ);
-  const int64_t slots = (int64_t)occ * num_cu();
+  const int64_t slots = (int64_t)occ * tb::num_cu();
   const int stages = (Kmax + KC - 1) / KC;
   double best = 1e30;
   int ns = 1;
@@ -442,18 +351,9 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
 }
 
 template <int BM, int BP, int WGM>
-hipError_t launch_tile(const CGArgs& a, hipStream_t st) {
+hipError_t launch(const CGArgs& a, hipStream_t st) {
   const int64_t nb = (int64_t)a.mtiles * a.ptiles * a.nsplit * a.ncls;
-  const size_t lds = lds_bytes(BM, BP);
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [&] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_gemm<BM, BP, WGM>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_conv_gemm<BM, BP, WGM>), dim3((unsigned)nb), dim3(NTH), lds, st, a);
-  return hipGetLastError();
+  return launch_tile<&k_conv_gemm<BM, BP, WGM>>(lds_bytes(BM, BP), nb, a, st);
 }
 
 }  // namespace
@@ -489,11 +389,9 @@ int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, co
   }
   a.part = wsf + align_floats(pl.pack_floats);
   hipError_t e = hipSuccess;
-  if (pl.BM == 32) e = launch_tile<32, 128, 1>(a, st);
-  else if (pl.BM == 64 && pl.BP == 64) e = launch_tile<64, 64, 2>(a, st);
-  else if (pl.BM == 64) e = launch_tile<64, 128, 2>(a, st);
-  else if (pl.BP == 64) e = launch_tile<128, 64, 2>(a, st);
-  else e = launch_tile<128, 128, 2>(a, st);
+  if (pl.BM == 32) e = launch<32, 128, 1>(a, st);
+  else if (pl.BM == 64) e = launch<64, 64, 2>(a, st);
+  else e = launch<128, 128, 2>(a, st);
   if (e != hipSuccess) return TB_ERR_HIP;
   if (a.nsplit > 1) {
     const int64_t tot = (int64_t)a.ncls * a.M * a.P;

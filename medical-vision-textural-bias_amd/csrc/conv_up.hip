@@ -22,6 +22,7 @@
 
 #include <cstdlib>
 
+#include "num_cu.h"
 #include "texbias.h"
 
 namespace {
@@ -311,18 +312,9 @@ __global__ __launch_bounds__(NTH) void k_convT_fewout(TArgs a) {
   }
 }
 
-int ncu_count() {
-  static const int n = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1) c = 256;
-    return c;
-  }();
-  return n;
-}
-
 // z segment length for `base` blocks per z segment, `per_cu` blocks resident per CU: rounds x (len + fill)
 int zseg(int D, int base, int per_cu, int fill) {
-  const int slots = per_cu * ncu_count();
+  const int slots = per_cu * tb::num_cu();
   int best = 1 << 30, zl = D;
   for (int l = D; l >= 1; --l) {
     const int zs = (D + l - 1) / l, rounds = (base * zs + slots - 1) / slots, cost = rounds * (l + fill);
@@ -736,8 +728,8 @@ static int fwd16_call(const float* x, const float* W, const float* bias, const f
   constexpr int persist_env = 1;
   a.ncol = N * a.nyb;
   unsigned nblk = (unsigned)(N * a.nyb * a.ZS);
-  a.persist = persist_env && per_cu == 1 && (int64_t)a.ncol * D >= 8LL * ncu_count() && nblk % ncu_count() != 0;
-  if (a.persist) nblk = (unsigned)ncu_count();
+  a.persist = persist_env && per_cu == 1 && (int64_t)a.ncol * D >= 8LL * tb::num_cu() && nblk % tb::num_cu() != 0;
+  if (a.persist) nblk = (unsigned)tb::num_cu();
   hipLaunchKernelGGL(kern, dim3(nblk), dim3(NTv), lds, reinterpret_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
 }

@@ -25,6 +25,7 @@
 
 #include <cstdlib>
 
+#include "num_cu.h"
 #include "texbias.h"
 
 namespace {
@@ -1454,61 +1455,41 @@ int tb_conv3d_wgrad_f32(const float* G, const float* X, float* dW, int N, int M,
   if (!G || !X || !dW) return TB_ERR_INVALID_ARG;
   hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
   if (pad == 1 && N >= 1 && use_zm(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    static const int ncu = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-      return n;
-    }();
     ZmArgs z{};
     size_t lds = 0;
     dim3 grid;
-    if (zm_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, ncu) == TB_OK) {
+    if (zm_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, tb::num_cu()) == TB_OK) {
       z.G = G; z.X = X; z.dW = dW;
       if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
       return launch_zm(z, lds, grid, st0);
     }
   }
   if (pad == 1 && N >= 1 && use_zm2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    static const int ncu2 = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-      return n;
-    }();
     Zm2Args z{};
     size_t lds = 0;
     dim3 grid;
-    if (zm2_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, ncu2) == TB_OK) {
+    if (zm2_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, tb::num_cu()) == TB_OK) {
       z.G = G; z.X = X; z.dW = dW;
       if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
       return launch_zm2(z, lds, grid, st0);
     }
   }
   if (pad == 1 && N >= 1 && use_zf1(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    static const int ncu4 = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-      return n;
-    }();
     Zf1Args z{};
     size_t lds = 0;
     dim3 grid;
-    if (zf1_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, ncu4) == TB_OK) {
+    if (zf1_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, tb::num_cu()) == TB_OK) {
       z.G = G; z.X = X; z.dW = dW;
       if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
       return launch_zf1(z, lds, grid, st0);
     }
   }
   if (pad == 1 && N >= 1 && use_zf2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    static const int ncu3 = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-      return n;
-    }();
     Zf2Args z{};
     int MT = 1;
     size_t lds = 0;
     dim3 grid;
-    if (zf2_setup(z, MT, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, ncu3) == TB_OK) {
+    if (zf2_setup(z, MT, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, tb::num_cu()) == TB_OK) {
       z.G = G; z.X = X; z.dW = dW;
       if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
       return launch_zf2(z, MT, lds, grid, st0);
@@ -1535,15 +1516,6 @@ int tb_conv3d_wgrad_f32(const float* G, const float* X, float* dW, int N, int M,
   return TX == 1 ? launch_seg<2, 1>(a, seg, by, lds, st) : launch_seg<2, 3>(a, seg, by, lds, st);
 }
 
-static int wgrad_ncu() {
-  static const int n = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1) c = 256;
-    return c;
-  }();
-  return n;
-}
-
 // The z-marching route tb_conv3d_wgrad_f32 takes for these sizes, set up for partial tiles: the partial
 // tile of each workgroup is TM x TC x 27 floats (k_wgrad_reduce), `blocks` workgroups per tile.
 struct ZRoute {
@@ -1563,7 +1535,7 @@ static ZRoute zroute(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int H
                      const void* G, const void* X) {
   ZRoute r;
   if (pad != 1 || N < 1) return r;
-  const int ncu = wgrad_ncu();
+  const int ncu = tb::num_cu();
   if (use_zm(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X) &&
       zm_setup(r.zm, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, ncu) == TB_OK) {
     r.kind = 1, r.TM = 16, r.TC = 16, r.ctiles = r.zm.ctiles;

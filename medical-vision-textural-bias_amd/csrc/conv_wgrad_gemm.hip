@@ -21,9 +21,7 @@
 // 128-B row segments per load -- through buffer descriptors whose range check returns 0 for a masked q
 // (offset 2^31), a row past the tensor's end, and the tail of a sample, without selects on loaded values.
 // Rows past M / C inside the range read some other channel; they only feed output rows / columns that are
-// never stored.  Everything after the stagers is k_conv_gemm's loop: LDS tiles [row][32 q + 4 pad],
-// 16-B LDS reads, mfma_f32_32x32x2f32 (exact f32, one rounding per product), two stage buffers with one
-// barrier per stage and the loads of stage s + 2 in flight in registers.
+// never stored.  Everything after the stagers is the tile pipeline of gemm_core.h.
 //
 // The reduction is cut into slices of whole stages that never straddle a sample; every block writes its
 // partial tile to the caller's workspace [slice][m][t C + c], and k_wgg_reduce sums the slices in order
@@ -31,20 +29,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
-#include <type_traits>
 
+#include "gemm_core.h"
+#include "num_cu.h"
 #include "texbias.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace tb::gemm;
 
-constexpr int KC = 32;    // q per stage
-constexpr int NTH = 256;  // threads per block
-constexpr int RS = 36;    // LDS floats per tile row: 32 q + 4 pad (16-B reads of 16 rows hit distinct banks)
-constexpr int RC = 64;    // X channels per reduce block
+constexpr int RC = 64;  // X channels per reduce block
 
 struct WGArgs {
   const float* g;
@@ -62,20 +56,11 @@ struct WGArgs {
   int nsplit;              // N sps
 };
 
-__device__ __forceinline__ int xcd_remap(int b, int nb) {
-  // hardware dispatch sends block b to XCD b % 8: give XCD x the contiguous logical range of blocks
-  const int q = nb >> 3, r = nb & 7, x = b & 7, i = b >> 3;
-  return x < r ? x * (q + 1) + i : r * (q + 1) + (x - r) * q + i;
-}
-
 template <int BM, int BP>
 __global__ __launch_bounds__(NTH) void k_conv_wgrad_gemm(const WGArgs a) {
-  constexpr int WGM = 2;
-  constexpr int TM = BM / WGM / 32, TN = BP / (4 / WGM) / 32;
+  using TileT = Tile<BM, BP, 2>;
   constexpr int AR = BM / 8, BR = BP / 8;  // rows per thread per stage
-  static_assert(TM >= 1 && TN >= 1, "tile");
   extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
-  constexpr int LBUF = (BM + BP) * RS;  // floats per stage buffer
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ql = tid & 31, rg = tid >> 5;
@@ -103,8 +88,8 @@ __global__ __launch_bounds__(NTH) void k_conv_wgrad_gemm(const WGArgs a) {
   const uint32_t bbase = 4u * ((uint32_t)(n * a.xsn) + (uint32_t)(c0 + rg) * (uint32_t)a.XS);
   const uint32_t arow = 32u * (uint32_t)Q, brow = 32u * (uint32_t)a.XS;
 
-  // two register slots: the loads of stage s + 2 are in flight while stage s runs from LDS and stage
-  // s + 1 (loaded one stage earlier) is written to the other LDS buffer
+  // the stagers' two register slots (gemm_core.h); stage s holds q = 32 (sb + s) .. + 31 of sample n, and
+  // a stage past the slice or a q past the sample reads zeros
   float ra[2][AR], rb[2][BR];
   auto gload = [&](auto SL, int s) {
     constexpr int sl = decltype(SL)::value;
@@ -125,87 +110,29 @@ __global__ __launch_bounds__(NTH) void k_conv_wgrad_gemm(const WGArgs a) {
     for (int i = 0; i < BR; ++i)
       rb[sl][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)(bv + i * brow), 0, 0));
   };
-  auto stage_store = [&](auto SL) {  // slot sl -> LDS buffer sl (stage s uses slot and buffer s & 1)
+  auto store = [&](auto SL) {
     constexpr int sl = decltype(SL)::value;
-    float* L = lds_dyn + sl * LBUF + rg * RS + ql;
+    float* L = lds_dyn + sl * TileT::LBUF + rg * RS + ql;
 #pragma unroll
     for (int i = 0; i < AR; ++i) L[8 * i * RS] = ra[sl][i];
 #pragma unroll
     for (int i = 0; i < BR; ++i) L[(BM + 8 * i) * RS] = rb[sl][i];
   };
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  TileT tile(w, lane);
+  __builtin_assume(nst > 0);  // a slice starts inside its sample (make_plan): no guard round the prologue
+  tile.run(lds_dyn, nst, gload, store);
 
-  const int wm = w % WGM, wn = w / WGM;
-  const int kk = lane >> 5, l32 = lane & 31;
-  // steps h*8 .. h*8+7 of the stage in LDS buffer sl (MFMA step st pairs q = st with q = 16 + st)
-  auto compute_half = [&](auto SL, auto H) {
-    constexpr int sl = decltype(SL)::value, h = decltype(H)::value;
-    const float* L = lds_dyn + sl * LBUF;
-    f32x4 af[TM][2], bf[TN][2];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const float* src = L + ((wm * TM + tm) * 32 + l32) * RS + 16 * kk + 8 * h;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) af[tm][q] = *reinterpret_cast<const f32x4*>(src + 4 * q);
-    }
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      const float* src = L + (BM + (wn * TN + tn) * 32 + l32) * RS + 16 * kk + 8 * h;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) bf[tn][q] = *reinterpret_cast<const f32x4*>(src + 4 * q);
-    }
-#pragma unroll
-    for (int st = 0; st < 8; ++st)
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tm][st >> 2][st & 3], bf[tn][st >> 2][st & 3],
-                                                             acc[tm][tn], 0, 0, 0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  gload(I0{}, 0);
-  stage_store(I0{});
-  gload(I1{}, 1);
-  __syncthreads();
-  // stage s: its first 8 MFMA steps, then the loads of stage s + 2 (past the slice they read zeros through
-  // the descriptors' range check: no branches), the last 8 steps, stage s + 1 to the other LDS buffer
-  auto body = [&](auto SL, int s) {
-    using O = std::integral_constant<int, 1 - decltype(SL)::value>;
-    compute_half(SL, I0{});
-    gload(SL, s + 2);
-    compute_half(SL, I1{});
-    stage_store(O{});
-    __syncthreads();
-  };
-  for (int s = 0; s < nst; s += 2) {
-    body(I0{}, s);
-    if (s + 1 < nst) body(I1{}, s + 1);
-  }
-
-  // epilogue: C column = X channel (lane & 31), rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  const int J = a.T * a.C;
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int c = c0 + (wn * TN + tn) * 32 + l32;
-    if (c >= a.C) continue;
-    float* dst = a.part + (int64_t)slice * a.M * J + t * a.C + c;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-        if (m < a.M) dst[(int64_t)m * J] = acc[tm][tn][r];
-      }
-  }
+  // column = X channel, row = G channel
+  const int M = a.M, C = a.C, J = a.T * C;
+  tile.epilogue([&](int col) {
+    const int c = c0 + col;
+    float* dst = a.part + (int64_t)slice * M * J + t * C + c;
+    return [=](int row, float v) {
+      const int m = m0 + row;
+      if (c < C && m < M) dst[(int64_t)m * J] = v;
+    };
+  });
 }
 
 // dW[m][c][t] = the slices' partials [slice][m][t C + c] summed in slice order; block (m, 64 channels):
@@ -229,26 +156,12 @@ __global__ __launch_bounds__(256) void k_wgg_reduce(const WGArgs a) {
   for (int i = (int)threadIdx.x; i < nc * T; i += 256) dst[i] = sh[i];
 }
 
-int g_ncu = 0;
-int num_cu() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&g_ncu, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess)
-      g_ncu = 256;
-  });
-  return g_ncu > 0 ? g_ncu : 256;
-}
-
 struct Plan {
   WGArgs a;
   int BM, BP;
   int64_t blocks;
   size_t part_floats;
 };
-
-inline size_t lds_bytes(int BM, int BP) { return (size_t)2 * (BM + BP) * RS * sizeof(float); }
 
 // Geometry and tiling of a call (no device pointers).  force_sps > 0 overrides the planned slices per sample.
 int make_plan(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int ksize,
@@ -276,7 +189,7 @@ int make_plan(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int W
   // slices per sample: the most loaded CU's blocks x (stages per block + a fixed per-block cost of ~3
   // stages) at the matrix-core rate of one BM x BP stage (two blocks per CU hide each other's LDS phases,
   // one does not), plus the partials written once and read once at ~3 TB/s; ties keep the smaller split
-  const int ncu = num_cu();
+  const int ncu = tb::num_cu();
   const double t_stage = (double)pl.BM * pl.BP * 2 * KC / 614e3;  // us at a CU's f32 MFMA peak
   const double part_us = (double)N * M * a.T * C * 8 / 3.0e6;     // per slice per sample
   double best = 1e30;
@@ -299,17 +212,8 @@ int make_plan(int N, int M, int C, int Do, int Ho, int Wo, int Di, int Hi, int W
 }
 
 template <int BM, int BP>
-hipError_t launch_tile(const WGArgs& a, int64_t nb, hipStream_t st) {
-  const size_t lds = lds_bytes(BM, BP);
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [&] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wgrad_gemm<BM, BP>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_conv_wgrad_gemm<BM, BP>), dim3((unsigned)nb), dim3(NTH), lds, st, a);
-  return hipGetLastError();
+hipError_t launch(const WGArgs& a, int64_t nb, hipStream_t st) {
+  return launch_tile<&k_conv_wgrad_gemm<BM, BP>>(lds_bytes(BM, BP), nb, a, st);
 }
 
 }  // namespace
@@ -345,10 +249,10 @@ int tb_conv3d_wgrad_gemm_ex_f32(const float* G, int64_t gsn, const float* X, int
   a.part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipError_t e;
-  if (pl.BM == 64 && pl.BP == 64) e = launch_tile<64, 64>(a, pl.blocks, st);
-  else if (pl.BM == 64) e = launch_tile<64, 128>(a, pl.blocks, st);
-  else if (pl.BP == 64) e = launch_tile<128, 64>(a, pl.blocks, st);
-  else e = launch_tile<128, 128>(a, pl.blocks, st);
+  if (pl.BM == 64 && pl.BP == 64) e = launch<64, 64>(a, pl.blocks, st);
+  else if (pl.BM == 64) e = launch<64, 128>(a, pl.blocks, st);
+  else if (pl.BP == 64) e = launch<128, 64>(a, pl.blocks, st);
+  else e = launch<128, 128>(a, pl.blocks, st);
   if (e != hipSuccess) return TB_ERR_HIP;
   hipLaunchKernelGGL(k_wgg_reduce, dim3((unsigned)M, (unsigned)((C + RC - 1) / RC)), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;

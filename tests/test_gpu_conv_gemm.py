@@ -61,8 +61,11 @@ def test_conv_dgrad_s1(conv, cin, cout, shape, s, k):
     close64(gx, gxr, gx64)
 
 
-@pytest.mark.parametrize("cin,cout,shape", [(384, 64, (2, 5, 5, 4)), (128, 32, (1, 6, 4, 6)), (64, 16, (2, 3, 4, 4)),
-                                            (32, 12, (1, 5, 3, 7)), (8, 40, (2, 2, 3, 5)), (16, 4, (1, 3, 3, 4))])
+CONVT = [(384, 64, (2, 5, 5, 4)), (128, 32, (1, 6, 4, 6)), (64, 16, (2, 3, 4, 4)), (32, 12, (1, 5, 3, 7)),
+         (8, 40, (2, 2, 3, 5)), (16, 4, (1, 3, 3, 4))]
+
+
+@pytest.mark.parametrize("cin,cout,shape", CONVT)
 def test_convT_forward(conv, cin, cout, shape):
     torch.manual_seed(2)
     x = torch.randn((shape[0], cin) + shape[1:], device="cuda")
@@ -90,6 +93,36 @@ def test_conv_s2_dgrad(conv, cin, cout, shape):
     gx = conv.conv_gemm(g.float(), w.float(), None, "convT", 2, 3)
     assert gx.shape == x.shape
     close64(gx, gxr, gx64)
+
+
+CONVT_EMPTY = (384, 64, (2, 5, 5, 4))
+
+
+def test_shape_lists_reach_pipeline_corners(conv):
+    """No kernel runs: the planner's answers (tb_conv3d_gemm_config) for the shape lists above.  The tile
+    pipeline (csrc/gemm_core.h) runs stages in pairs with an odd tail, and a block of a sub-pixel class
+    whose K ends before its k slice runs no stage at all; the cases above must keep reaching all three."""
+    stages = set()
+    for cin, cout, shape, s, k in CONV:
+        cfg = conv.conv_gemm_config((shape[0], cin) + shape[1:], cout, "conv", s, k)
+        assert cfg["kper"] % 32 == 0
+        stages.add(cfg["kper"] // 32)
+    assert any(n % 2 == 1 for n in stages), stages  # the odd tail
+    assert any(n % 2 == 0 for n in stages), stages  # whole pairs
+    assert CONVT_EMPTY in CONVT
+    cin, cout, shape = CONVT_EMPTY
+    cfg = conv.conv_gemm_config((shape[0], cin) + shape[1:], cout, "convT", 2, 3)
+    # the one-tap class has K = cin: its last slice starts at or past it
+    assert cfg["nsplit"] > 1 and (cfg["nsplit"] - 1) * cfg["kper"] >= cin, cfg
+
+
+@pytest.mark.parametrize("mode,cin,cout,shape,s", [("conv", 128, 128, (1, 5, 5, 4), 1), ("convT",) + CONVT_EMPTY + (2,)])
+def test_bitwise_repeatable(conv, mode, cin, cout, shape, s):
+    torch.manual_seed(8)
+    x = torch.randn((shape[0], cin) + shape[1:], device="cuda")
+    w = torch.randn((cout, cin, 3, 3, 3) if mode == "conv" else (cin, cout, 3, 3, 3), device="cuda") * 0.02
+    b = torch.randn(cout, device="cuda")
+    assert torch.equal(conv.conv_gemm(x, w, b, mode, s, 3), conv.conv_gemm(x, w, b, mode, s, 3))
 
 
 def test_add_and_channel_slice(conv):
