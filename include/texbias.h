@@ -179,6 +179,27 @@ int tb_conv3d_wgrad_ws_f32(const float* G, const float* X, float* dW, int N, int
                            int Di, int Hi, int Wi, int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * tb_conv3d_wgrad_ws_f32 that can also deliver the bias gradient of a Conv3d (G = grad_out):
+ *   dbias[m] = sum_n,z,y,x G[n][m][z][y][x]          (device, M floats, overwritten; NULL: not wanted)
+ * out of the same sweep over G, where the chosen route stages every value of G once per workgroup:
+ * today the few-channel stride-1 route (M <= 3, Cc <= 5, Wo % 4 == 0, Wo <= 256, 16-B aligned G and X:
+ * the 3 -> 3 full-resolution unit).  Each workgroup sums its own rows and planes in float64 and writes M
+ * float64 partials behind its dW tile in `ws`; the reduction kernel adds them in a fixed order, so the
+ * sum is the same on every call and as accurate as tb_channel_sum_ws_f32 (no float atomics).
+ * tb_conv3d_wgrad_bias_ws_bytes: the workspace for these sizes INCLUDING the partials (>= the value
+ * of tb_conv3d_wgrad_ws_bytes; `ws` 8-byte aligned), and *sums_bias (NULL allowed) = 1 when the route
+ * for 16-B aligned operands sums the bias.  *bias_done (host int, NULL allowed) is set before the call
+ * returns: 1 when dbias was (is being, on `stream`) written, 0 when it was not touched -- dbias NULL,
+ * another route, misaligned operands, a workspace without room for the partials -- and the caller
+ * takes the bias gradient elsewhere (tb_channel_sum_ws_f32).  dW is produced either way.
+ */
+int64_t tb_conv3d_wgrad_bias_ws_bytes(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                      int pad, int* sums_bias);
+int tb_conv3d_wgrad_bias_ws_f32(const float* G, const float* X, float* dW, float* dbias, int N, int M, int Cc, int Do,
+                                int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad, void* ws, size_t ws_bytes,
+                                int* bias_done, void* stream);
+
+/*
  * The tiling tb_conv3d_wgrad_f32 chooses for these sizes, without launching anything (host only):
  * cfg[0] = SEG (64-column row segments staged per wave, 1..4), cfg[1] = TX (1: 16 input channels x
  * 27 tap accumulators; 3: (channel, tx) columns for <= 5 channels), cfg[2] = YB (output rows per

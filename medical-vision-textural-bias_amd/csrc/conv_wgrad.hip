@@ -509,10 +509,29 @@ __global__ __launch_bounds__(64 * NW) void k_conv3d_wgrad_zm(ZmArgs a) {
 // dW from per-workgroup partial tiles part[tile][nblk][TM m][TC c][27], summed in block order: 64 entries x
 // 16 block groups per 1024-thread workgroup (each thread ~nblk / 16 independent loads in flight), the groups
 // met in LDS.  grid (ceil(TM TC 27 / 64), tiles); tile -> (mt, ct) = (tile / ctiles, tile % ctiles).
+// With `bpart` (k_conv3d_wgrad_zf1's float64 channel sums [nblk][M]) one more workgroup in x sums them
+// into dbias[M]: each thread its blocks in order, then a fixed tree -- the same sum every call.
 __global__ __launch_bounds__(1024) void k_wgrad_reduce(const float* __restrict__ part, float* __restrict__ dW, int nblk,
-                                                       int TM, int TC, int ctiles, int M, int Cc) {
+                                                       int TM, int TC, int ctiles, int M, int Cc,
+                                                       const double* __restrict__ bpart, float* __restrict__ dbias) {
   __shared__ float red[16][64];
+  __shared__ double bred[1024];
   const int tid = (int)threadIdx.x, el = tid & 63, bg = tid >> 6;
+  if (bpart && blockIdx.x == gridDim.x - 1) {  // (the whole workgroup)
+    for (int m = 0; m < M; ++m) {
+      double s = 0.0;
+      for (int b = tid; b < nblk; b += 1024) s += bpart[(int64_t)b * M + m];
+      bred[tid] = s;
+      __syncthreads();
+      for (int w = 512; w; w >>= 1) {
+        if (tid < w) bred[tid] += bred[tid + w];
+        __syncthreads();
+      }
+      if (tid == 0) dbias[m] = (float)bred[0];
+      __syncthreads();
+    }
+    return;
+  }
   const int TE = TM * TC * 27, tile = (int)blockIdx.y;
   const int e = (int)blockIdx.x * 64 + el;
   const float* src = part + (int64_t)tile * nblk * TE + (e < TE ? e : 0);
@@ -910,21 +929,34 @@ __global__ __launch_bounds__(64 * NW) void k_conv3d_wgrad_zf2(Zf2Args a) {
 
 // Stride 1, few channels (9 M <= 32, 3 Cc <= 16: the 3->3 full-resolution layer).  MFMA rows are
 // (m, tz, ty) -- 27 of two 16-row tiles at M = 3 -- and columns (c, tx), so one k-step of 4 output
-// columns px of input row qy (plane qz) is 2 MFMAs (16x16x4 f32) reading 2 A values and 1 B value
-// per lane: A[(m, tz, ty)][px] = G[m][qz - tz + 1][qy - ty + 1][px], B[px][(c, tx)] =
-// X[c][qz][qy][px + tx - 1].  The block marches its (n, input row block, z segment) along qz: one
-// X plane (YB rows) and one G plane (YB + 2 rows) staged per step, G in a 4-slot ring; the next
-// step's slabs and the next k-step's operands are in flight while the MFMAs run.
+// columns px of input row qy (plane qz) is 2 MFMAs (16x16x4 f32) of 2 A values and 1 B value per lane:
+// A[(m, tz, ty)][px] = G[m][qz - tz + 1][qy - ty + 1][px], B[px][(c, tx)] = X[c][qz][qy][px + tx - 1].
+// The block marches its (n, input row block, z segment) along qz: one X plane (YB rows) and one G
+// plane (YB + 2 rows) staged per step, G in a 4-slot ring; the slabs of the next steps are in flight
+// in registers.
+// Operand path: the k slot lk = lane >> 4 of the s-th MFMA of a 16-column group g is px = 16 g + 4 lk + s
+// (any assignment of px to k slots is a valid one as long as A and B share it), so a lane's four A
+// values of a group are ONE 16-byte LDS read per tile and its four B values four consecutive floats;
+// a group is 8 MFMAs, and the reads of group g + 1 are in flight under the MFMAs of group g.  No read
+// is predicated: lanes of absent rows (r >= 9 M) and columns (>= 3 Cc) read row 0 / column 0 -- the
+// rows and columns of an MFMA result are independent and theirs are never stored -- and rows are
+// padded to whole groups with zeros in G.
+// Bias gradient: with `bpart` every thread also sums the G values it stages that are the block's own
+// (rows y0 .. y0 + YB - 1, planes [z0, z1): neither halo rows nor halo planes) in float64; the block
+// writes M float64 partials that k_wgrad_reduce sums in block order.
 struct Zf1Args {
   const float* G;
   const float* X;
   float* dW;
-  float* part;  // non-null: per-workgroup partial tiles (k_wgrad_reduce) instead of atomics
+  float* part;    // non-null: per-workgroup partial tiles (k_wgrad_reduce) instead of atomics
+  double* bpart;  // non-null: per-workgroup channel sums of G, [block][M]
   int N, M, Cc, D, H, W;
   int YB, nyb, ZS, zlen;
   int GR, GM, GS;  // G: row pitch, channel pitch, slot pitch (floats)
   int XR, XC, XS;  // X: row pitch (data at col 4), channel pitch, slot pitch
 };
+
+constexpr size_t ZF1_RED_BYTES = (size_t)2 * 4 * 4 * 64 * 4;  // the end reduction's image; 4 x 3 doubles follow
 
 template <int YB, int WV>  // input rows per block, W <= 4 WV
 __global__ __launch_bounds__(256) void k_conv3d_wgrad_zf1(Zf1Args a) {
@@ -934,26 +966,30 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad_zf1(Zf1Args a) {
   const int W = a.W, H = a.H, D = a.D, M = a.M, Cc = a.Cc;
   float* gsl = smem;               // [4 slots][m][YB + 2 rows][GR]
   float* xsl = smem + 4 * a.GS;    // [2 slots][c][YB rows][XR], x at col x + 4
+  f32x4* smem4 = reinterpret_cast<f32x4*>(smem);  // (the staging stores index 16-byte units: every pitch is one)
+  const int dump = a.GS + (a.XS >> 1) + tid;      // this thread's 16 bytes for the staging items it does not have
   int b = (int)blockIdx.x;
   const int zs = b % a.ZS;
   b /= a.ZS;
   const int yb = b % a.nyb, n = b / a.nyb;
   const int y0 = yb * YB;
   const int z0 = zs * a.zlen, z1 = min(D, z0 + a.zlen);
-  for (int i = tid; i < 4 * a.GS + 2 * a.XS; i += 256) smem[i] = 0.f;  // halos and absent rows stay 0
+  for (int i = tid; i < 4 * a.GS + 2 * a.XS; i += 256) smem[i] = 0.f;  // halos, pads and absent rows stay 0
+  // (the dump lines behind the slabs are only ever written)
   const int64_t plane = (int64_t)H * W, plane4 = plane / 4;
   const float* Gb = a.G + (int64_t)n * M * D * plane;
   const float* Xb = a.X + (int64_t)n * Cc * D * plane;
   const int W4v = W >> 2;
   constexpr int NXL = (5 * YB * WV + 255) / 256, NGL = (3 * (YB + 2) * WV + 255) / 256;
   int xg[NXL], xl[NXL], gg[NGL], gl[NGL];
+  bool own[NGL];  // a G item of the block's own rows (the bias sum counts it)
 #pragma unroll
   for (int j = 0; j < NXL; ++j) {
     const int i = tid + 256 * j;
     const int q = i % W4v, t = i / W4v, yy = t % YB, c = t / YB;
     const bool ok = c < Cc && y0 + yy < H;
     xg[j] = ok ? (int)(((int64_t)c * D) * plane4 + ((y0 + yy) * W + 4 * q) / 4) : -1;
-    xl[j] = c * a.XC + yy * a.XR + 4 + 4 * q;
+    xl[j] = ok ? a.GS + ((c * a.XC + yy * a.XR) >> 2) + 1 + q : dump;  // (from smem4; + slot XS / 4)
   }
 #pragma unroll
   for (int j = 0; j < NGL; ++j) {
@@ -962,110 +998,140 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad_zf1(Zf1Args a) {
     const int y = y0 - 1 + r;
     const bool ok = m < M && y >= 0 && y < H;
     gg[j] = ok ? (int)(((int64_t)m * D) * plane4 + (y * W + 4 * q) / 4) : -1;
-    gl[j] = m * a.GM + r * a.GR + 4 * q;
+    gl[j] = ok ? ((m * a.GM + r * a.GR) >> 2) + q : dump;  // (from smem4; + slot GS / 4)
+    own[j] = ok && r >= 1 && r <= YB;
   }
   // the slabs of the next ZP steps are in flight in registers (a step's MFMAs take less than an HBM
   // round trip): set p holds X[zi] and G[zi + 1] for the steps zi = p (mod ZP)
-  constexpr int ZP = 3;
-  float4 rx[ZP][NXL], rg[ZP][NGL];
-  auto load_x = [&](int zi, float4 (&r)[NXL]) {  // (planes past the segment: clamped, never stored)
-    const float4* src = reinterpret_cast<const float4*>(Xb) + (int64_t)(zi < D ? zi : D - 1) * plane4;
+  constexpr int ZP = 3;  // (native vectors: HIP's float4 struct, copied load -> array, left the sets in scratch)
+  f32x4 rx0[NXL], rx1[NXL], rx2[NXL], rg0[NGL], rg1[NGL], rg2[NGL];
+  double bs[NGL];
 #pragma unroll
-    for (int j = 0; j < NXL; ++j) {
-      const float4 v = src[xg[j] < 0 ? 0 : xg[j]];
-      r[j] = xg[j] < 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : v;
-    }
+  for (int j = 0; j < NGL; ++j) bs[j] = 0.0;
+  const bool bias = a.bpart != nullptr;
+  // Nothing may touch a loaded value before its slab is stored, ZP steps later: a select on it right
+  // after the load (zeros for absent items or planes) makes the wave wait for the load where it was
+  // issued, one HBM round trip per step with nothing in flight.  The stores are branch-free for the same
+  // reason (under per-item branches the register sets were copied at the loop edge, a wait for every
+  // load): an absent item loads a clamped address and is stored to the thread's dump line, a plane
+  // outside [0, D) is stored as zeros by a select at the store.
+  auto load_x = [&](int zi, f32x4 (&r)[NXL]) {  // (planes past the segment: clamped, never stored)
+    const f32x4* src = reinterpret_cast<const f32x4*>(Xb) + (int64_t)(zi < D ? zi : D - 1) * plane4;
+#pragma unroll
+    for (int j = 0; j < NXL; ++j) r[j] = src[xg[j] < 0 ? 0 : xg[j]];
   };
-  auto store_x = [&](int slot, const float4 (&r)[NXL]) {
+  auto store_x = [&](int slot, const f32x4 (&r)[NXL]) {
 #pragma unroll
     for (int j = 0; j < NXL; ++j)
-      if (xg[j] >= 0) *reinterpret_cast<float4*>(xsl + slot * a.XS + xl[j]) = r[j];
+      smem4[(xg[j] >= 0 ? slot * (a.XS >> 2) : 0) + xl[j]] = r[j];
   };
-  // (zero-selects at the load here: with three steps' slabs in flight the early wait costs nothing, and
-  // the store-side selects of k_conv3d_wgrad_zm measured slower for this kernel, 410 -> 430 us)
-  auto load_g = [&](int pz, float4 (&r)[NGL]) {  // G plane pz (zero outside [0, D))
+  auto load_g = [&](int pz, f32x4 (&r)[NGL]) {  // G plane pz (outside [0, D): a clamped plane, stored as zeros)
+    const f32x4* src = reinterpret_cast<const f32x4*>(Gb) + (int64_t)(pz >= 0 && pz < D ? pz : 0) * plane4;
+#pragma unroll
+    for (int j = 0; j < NGL; ++j) r[j] = src[gg[j] < 0 ? 0 : gg[j]];
+  };
+  auto store_g = [&](int slot, const f32x4 (&r)[NGL], int pz) {  // pz: the plane in r
     const bool in = pz >= 0 && pz < D;
-    const float4* src = reinterpret_cast<const float4*>(Gb) + (int64_t)(in ? pz : 0) * plane4;
+    const bool cnt = bias && pz >= z0 && pz < z1;  // every plane of the segment is stored exactly once
 #pragma unroll
     for (int j = 0; j < NGL; ++j) {
-      const float4 v = src[gg[j] < 0 ? 0 : gg[j]];
-      r[j] = (in && gg[j] >= 0) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+      const f32x4 v = in ? r[j] : f32x4{0.f, 0.f, 0.f, 0.f};  // (the one use of r[j]: a second one had the sets copied)
+      smem4[(gg[j] >= 0 ? slot * (a.GS >> 2) : 0) + gl[j]] = v;
+      const float q = (v[0] + v[1]) + (v[2] + v[3]);
+      bs[j] += (double)(own[j] && cnt ? q : 0.f);
     }
   };
-  auto store_g = [&](int slot, const float4 (&r)[NGL], int) {
-#pragma unroll
-    for (int j = 0; j < NGL; ++j)
-      if (gg[j] >= 0) *reinterpret_cast<float4*>(gsl + slot * a.GS + gl[j]) = r[j];
-  };
   __syncthreads();
-  load_g(z0 - 1, rg[0]);
-  store_g((z0 + 3) & 3, rg[0], z0 - 1);
-  load_g(z0, rg[0]);
-  store_g(z0 & 3, rg[0], z0);
-#pragma unroll
-  for (int p = 0; p < ZP; ++p) {
-    load_x(z0 + p, rx[p]);
-    load_g(z0 + p + 1, rg[p]);
-  }
-  // lane roles: A rows r = 16 t + (lane & 15) -> (m, tz, ty); B column (c, tx) = lane & 15; k = lane >> 4
+  load_g(z0 - 1, rg0);
+  store_g((z0 + 3) & 3, rg0, z0 - 1);
+  load_g(z0, rg0);
+  store_g(z0 & 3, rg0, z0);
+  load_x(z0, rx0);
+  load_g(z0 + 1, rg0);
+  load_x(z0 + 1, rx1);
+  load_g(z0 + 2, rg1);
+  load_x(z0 + 2, rx2);
+  load_g(z0 + 3, rg2);
+  // lane roles: A rows r = 16 t + (lane & 15) -> (m, tz, ty); B column (c, tx) = lane & 15; k slot lane >> 4
+  // = columns 4 lk .. 4 lk + 3 of each 16-column group
   const int li = lane & 15, lk = lane >> 4;
   int atz[2], aoff[2];
-  bool aok[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const int r = 16 * t + li, m = r / 9, tz = (r / 3) % 3, ty = r % 3;
-    aok[t] = m < M;
+    const int r0 = 16 * t + li, r = r0 < 9 * M ? r0 : 0;
+    const int m = r / 9, tz = (r / 3) % 3, ty = r % 3;
     atz[t] = tz;
-    aoff[t] = aok[t] ? m * a.GM + (2 - ty) * a.GR + lk : 0;  // G row y0 - 1 + (yy - ty + 2)
+    aoff[t] = m * a.GM + (2 - ty) * a.GR + 4 * lk;  // G row y0 - 1 + (yy - ty + 2)
   }
-  const int bc = li / 3, btx = li - 3 * bc;
-  const bool bok = bc < Cc;
-  const int boff = bok ? bc * a.XC + 3 + btx + lk : 0;  // X col px + tx - 1 at +4
-  const int kpr = W >> 2, np = 4 / YB, yy = wave % YB, part = wave / YB;
-  const int kb = (kpr * part) / np, ke = (kpr * (part + 1)) / np;
+  const int col = li < 3 * Cc ? li : 0, bc = col / 3, btx = col - 3 * bc;
+  const int boff = bc * a.XC + 3 + btx + 4 * lk;  // X col px + tx - 1 at +4
+  const int ngr = (W + 15) >> 4, np = 4 / YB, yy = wave % YB, part = wave / YB;
+  const int gb = (ngr * part) / np, ge = (ngr * (part + 1)) / np;
   f32x4 acc[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) acc[0][t] = acc[1][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto step = [&](int zi, float4 (&rxp)[NXL], float4 (&rgp)[NGL]) {
+  auto mm = [&](const f32x4& v0, const f32x4& v1, const f32x4& u) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      acc[s & 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0[s], u[s], acc[s & 1][0], 0, 0, 0);
+      acc[s & 1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1[s], u[s], acc[s & 1][1], 0, 0, 0);
+    }
+  };
+  auto step = [&](int zi, f32x4 (&rxp)[NXL], f32x4 (&rgp)[NGL]) {
     store_x(zi & 1, rxp);
     store_g((zi + 1) & 3, rgp, zi + 1);
     __syncthreads();
-    if (zi + ZP < z1) {
-      load_x(zi + ZP, rxp);
-      load_g(zi + ZP + 1, rgp);
-    }
+    // (unconditionally -- past the segment a clamped, never-stored plane: a conditional load leaves a
+    // wait for it at the join)
+    load_x(zi + ZP, rxp);
+    load_g(zi + ZP + 1, rgp);
     // G plane qz - tz + 1 sits in slot (zi + 1 - tz) & 3
-    const float* ga0 = gsl + ((zi + 1 - atz[0]) & 3) * a.GS + aoff[0] + yy * a.GR;
-    const float* ga1 = gsl + ((zi + 1 - atz[1]) & 3) * a.GS + aoff[1] + yy * a.GR;
+    const f32x4* ga0 = reinterpret_cast<const f32x4*>(gsl + ((zi + 1 - atz[0]) & 3) * a.GS + aoff[0] + yy * a.GR);
+    const f32x4* ga1 = reinterpret_cast<const f32x4*>(gsl + ((zi + 1 - atz[1]) & 3) * a.GS + aoff[1] + yy * a.GR);
     const float* xb = xsl + (zi & 1) * a.XS + boff + yy * a.XR;
-    auto ld = [&](int k, float& v0, float& v1, float& u) {
-      const int px = 4 * (k < ke ? k : ke - 1);
-      v0 = aok[0] ? ga0[px] : 0.f;
-      v1 = aok[1] ? ga1[px] : 0.f;
-      u = bok ? xb[px] : 0.f;
+    auto ld = [&](int g, f32x4& v0, f32x4& v1, f32x4& u) {
+      v0 = ga0[4 * g];
+      v1 = ga1[4 * g];
+      const float* p = xb + 16 * g;
+      u = f32x4{p[0], p[1], p[2], p[3]};
     };
-    if (kb < ke) {
-      float p0, p1, pu, q0, q1, qu;
-      ld(kb, p0, p1, pu);
-      int k = kb;
-      for (; k + 1 < ke; k += 2) {
-        ld(k + 1, q0, q1, qu);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(p0, pu, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(p1, pu, acc[0][1], 0, 0, 0);
-        ld(k + 2, p0, p1, pu);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(q0, qu, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(q1, qu, acc[1][1], 0, 0, 0);
+    if (gb < ge) {
+      f32x4 p0, p1, pu, q0, q1, qu;
+      ld(gb, p0, p1, pu);
+      int g = gb;
+      // (scheduling fences: left alone the compiler sinks a group's reads below the previous group's
+      // MFMAs and waits for them at once)
+      for (; g + 2 < ge; g += 2) {
+        ld(g + 1, q0, q1, qu);
+        __builtin_amdgcn_sched_barrier(0);
+        mm(p0, p1, pu);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(g + 2, p0, p1, pu);
+        __builtin_amdgcn_sched_barrier(0);
+        mm(q0, q1, qu);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      if (k < ke) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(p0, pu, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(p1, pu, acc[0][1], 0, 0, 0);
+      if (g + 1 < ge) {  // (peeled tail: one or two groups left, no clamped read)
+        ld(g + 1, q0, q1, qu);
+        __builtin_amdgcn_sched_barrier(0);
+        mm(p0, p1, pu);
+        mm(q0, q1, qu);
+      } else {
+        mm(p0, p1, pu);
       }
     }
   };
-  for (int zi = z0; zi < z1; zi += ZP) {
-    step(zi, rx[0], rg[0]);
-    if (zi + 1 < z1) step(zi + 1, rx[1], rg[1]);
-    if (zi + 2 < z1) step(zi + 2, rx[2], rg[2]);
+  // whole triples in the loop, the rest after it: with the steps of a triple under conditions the loads
+  // in flight at the loop edge are not a fixed count, and the first store of every triple waited for all
+  int zi = z0;
+  for (; zi + ZP <= z1; zi += ZP) {
+    step(zi, rx0, rg0);
+    step(zi + 1, rx1, rg1);
+    step(zi + 2, rx2, rg2);
+  }
+  if (zi < z1) {
+    step(zi, rx0, rg0);
+    if (zi + 1 < z1) step(zi + 1, rx1, rg1);
   }
   __syncthreads();
   float* red = smem;  // [2 tiles][4 waves][4 rr][64 lanes]
@@ -1073,7 +1139,21 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad_zf1(Zf1Args a) {
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) red[((t * 4 + wave) * 4 + rr) * 64 + lane] = acc[0][t][rr] + acc[1][t][rr];
+  double* bred = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + ZF1_RED_BYTES);  // [4 waves][3 m]
+  if (bias) {
+#pragma unroll
+    for (int mm_ = 0; mm_ < 3; ++mm_) {
+      double v = 0.0;
+#pragma unroll
+      for (int j = 0; j < NGL; ++j) v += ((tid + 256 * j) / W4v) / (YB + 2) == mm_ ? bs[j] : 0.0;
+#pragma unroll
+      for (int off = 32; off; off >>= 1) v += __shfl_down(v, off);
+      if (lane == 0) bred[wave * 3 + mm_] = v;
+    }
+  }
   __syncthreads();
+  if (bias && tid < M)
+    a.bpart[(int64_t)blockIdx.x * M + tid] = (bred[tid] + bred[3 + tid]) + (bred[6 + tid] + bred[9 + tid]);
   float* pt = a.part ? a.part + (int64_t)blockIdx.x * (M * Cc * 27) : nullptr;
   for (int e = tid; e < 2 * 4 * 64; e += 256) {  // e = (t, rr, lane)
     const int ln = e & 63, rr = (e >> 6) & 3, t = e >> 8;
@@ -1086,6 +1166,11 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad_zf1(Zf1Args a) {
     if (pt) pt[(m * Cc + c) * 27 + tz * 9 + ty * 3 + tx] = v;  // every (m < M, c < Cc) entry once
     else atomicAdd(&a.dW[((int64_t)m * Cc + c) * 27 + tz * 9 + ty * 3 + tx], v);
   }
+}
+
+int pad_mod(int v, int mod, int rem) {
+  while (v % mod != rem) ++v;
+  return v;
 }
 
 int pad_mod32(int v, int rem) {
@@ -1397,18 +1482,24 @@ bool use_zf1(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, 
 int zf1_setup(Zf1Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, int H, int W, int ncu) {
   a.N = N; a.M = M; a.Cc = Cc; a.D = D; a.H = H; a.W = W;
   constexpr int yb_env = 0;  // rows per block: the first tiling that fits (below)
-  // pitches: rows of one G channel 4 banks apart, channels and slots spread over the banks
-  a.GR = pad_mod32(W, 4);
-  a.XR = pad_mod32(W + 8, 4);
+  // rows hold whole 16-column groups (zeros past W).  G pitches for the 16-byte A reads, whose banks are
+  // taken mod 64 in four 16-lane groups: with row, channel and slot pitches = 40, 24, 56 (mod 64) the 16
+  // rows (m, tz, ty) of a tile are at most 2-way on a 16-byte slot for every ring phase (1.75 cycles per
+  // lane group on average; 4, 12, 20 mod 32 gave up to 4-way).  X pitches for the 4-byte B reads (banks
+  // mod 32, 32-lane halves): channels 8 banks apart, conflict-free up to 4 channels.
+  const int Wp = (W + 15) & ~15;
+  a.GR = pad_mod(Wp, 64, 40);
+  a.XR = pad_mod32(Wp + 8, 4);
   a.YB = 0;
   for (int yb : {2, 4, 1}) {
     if (yb_env && yb != yb_env) continue;
-    const int gm = pad_mod32((yb + 2) * a.GR, 12), gs = pad_mod32(M * gm, 20);
+    const int gm = pad_mod((yb + 2) * a.GR, 64, 24), gs = pad_mod(M * gm, 64, 56);
     const int xc = pad_mod32(yb * a.XR, 8), xs = pad_mod32(Cc * xc, 16);
-    const size_t bytes = (size_t)4 * (4 * gs + 2 * xs);
+    const size_t bytes = (size_t)4 * (4 * gs + 2 * xs + 4 * 256);  // + a 16-byte dump line per thread
     if (bytes <= 81920) {  // two blocks per CU
       a.YB = yb; a.GM = gm; a.GS = gs; a.XC = xc; a.XS = xs;
-      lds = bytes > (size_t)2 * 4 * 4 * 64 * 4 ? bytes : (size_t)2 * 4 * 4 * 64 * 4;
+      const size_t red = ZF1_RED_BYTES + 4 * 3 * sizeof(double);  // the end reduction's image
+      lds = bytes > red ? bytes : red;
       break;
     }
   }
@@ -1557,25 +1648,55 @@ int64_t tb_conv3d_wgrad_ws_bytes(int N, int M, int Cc, int Do, int Ho, int Wo, i
   return (int64_t)zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, nullptr, nullptr).bytes();
 }
 
-int tb_conv3d_wgrad_ws_f32(const float* G, const float* X, float* dW, int N, int M, int Cc, int Do, int Ho, int Wo,
-                           int Di, int Hi, int Wi, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+// the bias partials follow the partial tiles, 8-byte aligned: [grid.x][M] float64 (only the zf1 route)
+static size_t bias_off(const ZRoute& r) { return (r.bytes() + 7) & ~(size_t)7; }
+static size_t bias_bytes(const ZRoute& r, int M) { return r.kind == 3 ? (size_t)r.grid.x * M * sizeof(double) : 0; }
+
+int64_t tb_conv3d_wgrad_bias_ws_bytes(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
+                                      int pad, int* sums_bias) {
+  const ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, nullptr, nullptr);
+  const size_t bb = bias_bytes(r, M);
+  if (sums_bias) *sums_bias = bb ? 1 : 0;
+  return (int64_t)(bb ? bias_off(r) + bb : r.bytes());
+}
+
+int tb_conv3d_wgrad_bias_ws_f32(const float* G, const float* X, float* dW, float* dbias, int N, int M, int Cc, int Do,
+                                int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad, void* ws, size_t ws_bytes,
+                                int* bias_done, void* stream) {
+  if (bias_done) *bias_done = 0;
   if (!G || !X || !dW) return TB_ERR_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, G, X);
   if (!ws || !r.kind || ws_bytes < r.bytes() || (reinterpret_cast<uintptr_t>(ws) & 3) != 0)
     return tb_conv3d_wgrad_f32(G, X, dW, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, stream);
   float* part = static_cast<float*>(ws);
+  double* bpart = nullptr;
+  if (dbias && bias_bytes(r, M) && ws_bytes >= bias_off(r) + bias_bytes(r, M) &&
+      (reinterpret_cast<uintptr_t>(ws) & 7) == 0)
+    bpart = reinterpret_cast<double*>(static_cast<char*>(ws) + bias_off(r));
   int rc = TB_OK;
   switch (r.kind) {
     case 1: r.zm.G = G, r.zm.X = X, r.zm.dW = dW, r.zm.part = part; rc = launch_zm(r.zm, r.lds, r.grid, st); break;
     case 2: r.zm2.G = G, r.zm2.X = X, r.zm2.dW = dW, r.zm2.part = part; rc = launch_zm2(r.zm2, r.lds, r.grid, st); break;
-    case 3: r.zf1.G = G, r.zf1.X = X, r.zf1.dW = dW, r.zf1.part = part; rc = launch_zf1(r.zf1, r.lds, r.grid, st); break;
+    case 3:
+      r.zf1.G = G, r.zf1.X = X, r.zf1.dW = dW, r.zf1.part = part, r.zf1.bpart = bpart;
+      rc = launch_zf1(r.zf1, r.lds, r.grid, st);
+      break;
     default: r.zf2.G = G, r.zf2.X = X, r.zf2.dW = dW, r.zf2.part = part; rc = launch_zf2(r.zf2, r.MT, r.lds, r.grid, st); break;
   }
   if (rc != TB_OK) return rc;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3((r.TM * r.TC * 27 + 63) / 64, r.grid.y), dim3(1024), 0, st,
-                     static_cast<const float*>(part), dW, (int)r.grid.x, r.TM, r.TC, r.ctiles, M, Cc);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((r.TM * r.TC * 27 + 63) / 64 + (bpart ? 1 : 0), r.grid.y), dim3(1024), 0, st,
+                     static_cast<const float*>(part), dW, (int)r.grid.x, r.TM, r.TC, r.ctiles, M, Cc,
+                     static_cast<const double*>(bpart), dbias);
+  if (hipGetLastError() != hipSuccess) return TB_ERR_HIP;
+  if (bias_done) *bias_done = bpart ? 1 : 0;
+  return TB_OK;
+}
+
+int tb_conv3d_wgrad_ws_f32(const float* G, const float* X, float* dW, int N, int M, int Cc, int Do, int Ho, int Wo,
+                           int Di, int Hi, int Wi, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+  return tb_conv3d_wgrad_bias_ws_f32(G, X, dW, nullptr, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, ws, ws_bytes,
+                                     nullptr, stream);
 }
 
 // The tiling tb_conv3d_wgrad_f32 would choose (no launch): cfg = {SEG, TX, YB, chunks, LDS bytes}.

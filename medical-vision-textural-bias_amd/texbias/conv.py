@@ -58,6 +58,40 @@ def wgrad(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int) -> t
     return dW.view(w_shape)
 
 
+@functools.lru_cache(maxsize=256)
+def _wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad):
+    import ctypes
+    sums = ctypes.c_int(0)
+    nb = int(lib().tb_conv3d_wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, ctypes.byref(sums)))
+    return nb, bool(sums.value)
+
+
+def wgrad_bias(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int):
+    """``wgrad`` of a Conv3d (G = grad_out) and, where the route sums it out of the same sweep over G
+    (tb_conv3d_wgrad_bias_ws_f32, include/texbias.h), the bias gradient: (dW, gb) with gb [M] = G summed over the
+    batch and the positions, or (dW, None) when the route did not produce it (the caller then takes
+    ``channel_sum``)."""
+    import ctypes
+    G = G.contiguous()
+    X = X.contiguous()
+    N, M = G.shape[:2]
+    Cc = X.shape[1]
+    Do, Ho, Wo = G.shape[2:]
+    Di, Hi, Wi = X.shape[2:]
+    nb, sums = _wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad)
+    if not sums:
+        return wgrad(G, X, w_shape, stride, pad), None
+    dW = torch.empty((M, Cc, 3, 3, 3), dtype=torch.float32, device=G.device)
+    gb = torch.empty(M, dtype=torch.float32, device=G.device)
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=G.device)
+    done = ctypes.c_int(0)
+    with torch.cuda.device(G.device):
+        check(lib().tb_conv3d_wgrad_bias_ws_f32(G.data_ptr(), X.data_ptr(), dW.data_ptr(), gb.data_ptr(), N, M, Cc, Do, Ho,
+                                                Wo, Di, Hi, Wi, stride, pad, ws.data_ptr(), nb, ctypes.byref(done),
+                                                _stream(G)), "tb_conv3d_wgrad_bias_ws_f32")
+    return dW.view(w_shape), (gb if done.value else None)
+
+
 def wgrad_config(g_shape, x_shape, stride: int, pad: int = 1) -> dict:
     """The tiling ``wgrad`` picks for G [N, M, Do, Ho, Wo] / X [N, Cc, Di, Hi, Wi] (host only,
     tb_conv3d_wgrad_config): SEG, TX, YB, chunks, lds_bytes."""
@@ -687,10 +721,21 @@ class Route:
             list(self.output_padding), 1, [False, True, False])
         return gw
 
+    def weight_bias_grad(self, gy, x, w):
+        """(gw, gb_or_None): the weight gradient and, where its kernel sums grad_out on the way (``wgrad_bias``: the
+        few-channel stride-1 Conv3d route), the bias gradient; None from every other route."""
+        if not self.wgg and not self.transposed and self.fast_w and tuple(w.shape[2:]) == (3, 3, 3) and \
+                self.padding[0] == 1 and _wgrad_tiles(tuple(gy.shape), tuple(x.shape), self.stride[0]):
+            return wgrad_bias(gy, x, w.shape, self.stride[0], 1)
+        return self.weight_grad(gy, x, w), None
+
     def backward(self, gy, x, w, need_x: bool, need_w: bool, need_b: bool, gb=None):
         gy = gy.contiguous()
         gx = self.input_grad(gy, x, w) if need_x else None
-        gw = self.weight_grad(gy, x, w) if need_w else None
+        if need_w and need_b and gb is None:
+            gw, gb = self.weight_bias_grad(gy, x, w)
+        else:
+            gw = self.weight_grad(gy, x, w) if need_w else None
         if need_b and gb is None:
             gb = channel_sum(gy) if self.kind != "aten" else gy.sum(dim=(0, 2, 3, 4))
         return gx, gw, gb if need_b else None

@@ -94,8 +94,14 @@ class _ConvResFn(torch.autograd.Function):
         n = ctx.needs_input_grad
         g = g.contiguous()
         gx = ctx.route.input_grad(g, x, w, add=g) if n[0] else None
-        gw = ctx.route.weight_grad(g, x, w) if n[1] else None
-        gb = _conv.channel_sum(g) if ctx.has_b and n[2] else None
+        need_b = ctx.has_b and n[2]
+        gb = None
+        if n[1] and need_b:  # the weight-gradient sweep sums g on the way where its route can
+            gw, gb = ctx.route.weight_bias_grad(g, x, w)
+        else:
+            gw = ctx.route.weight_grad(g, x, w) if n[1] else None
+        if need_b and gb is None:
+            gb = _conv.channel_sum(g)
         return gx, gw, gb, None
 
 
