@@ -79,7 +79,10 @@ def test_unet_fused_matches_plain_modules(gpu, monkeypatch):
         assert err <= 2e-3 * max(b.abs().max().item(), 1e-4 * scale), (err, b.abs().max().item())
 
 
-@pytest.mark.parametrize("shape", [(2, 16, 24, 20, 16), (2, 3, 15, 15, 10), (1, 5, 33, 31, 7)])
+# the last three cross the 16384-voxel chunk of the reductions: S = 17408 (float4 access, one full chunk and a
+# ragged one), S = 16388 (a tail of exactly one float4), S = 17391 (scalar path over two chunks)
+@pytest.mark.parametrize("shape", [(2, 16, 24, 20, 16), (2, 3, 15, 15, 10), (1, 5, 33, 31, 7),
+                                   (1, 3, 17, 32, 32), (2, 2, 17, 241, 4), (1, 2, 33, 31, 17)])
 def test_adn_strided_residual_bias(gpu, shape):
     """tb_adn_fwd/bwd_f32 on channel slices of wider tensors (the stacked unit + residual conv output),
     the residual summed into the store, the producing conv's bias gradient (= dx summed over n and the
