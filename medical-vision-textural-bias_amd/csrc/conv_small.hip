@@ -20,6 +20,7 @@
 
 #include "texbias.h"
 #include "kernels.h"
+#include "num_cu.h"
 
 namespace {
 
@@ -108,142 +109,225 @@ __global__ __launch_bounds__(NT) void k_conv3d_small(const float* __restrict__ x
   }
 }
 
-// z-marching form: block = (n, ZB consecutive output planes z, ROWS rows of h).  The input planes
-// live in a 4-slot LDS ring ([slot][ci][ROWS + 2 rows][XP]); plane z + 2 is fetched by
-// global->LDS DMA (no registers, no waits) while plane z is computed from the slots of z - 1, z,
-// z + 1, so every input row is read from memory once per block instead of three times (once per tz
-// of each output plane) and its fetch hides under the previous plane's FMAs.
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
+// z-marching form: block = (n, zb consecutive output planes z, ROWS rows of h).  The input planes
+// live in a 3-slot LDS ring ([slot][ci][ROWS + 2 rows][XP]): step z computes plane z from the slots of
+// z - 1, z, z + 1 while plane z + 2 is on its way from memory into registers, and then puts it over
+// plane z - 1, so every input row is read from memory once per block instead of three times (once per
+// tz of each output plane).  Three slots are 48 KB at the C3 shape (3 channels, W = 160): three blocks
+// per CU, where a fourth slot (no barrier between the FMAs and the LDS store) allowed two.
+//
+// What the step's schedule rests on:
+//   * the next plane travels through registers (one wave per staged row, 4 bytes per lane, any W), is
+//     not touched between its load and its LDS store at the END of the step, and takes its zeros for
+//     out-of-range rows and planes in a select at that store.  (Fetched by global->LDS DMA the compiler
+//     has to treat it as a pending LDS write and drains vmcnt(0) before the step's first LDS read: the
+//     fetch, the residual loads and the previous step's stores were all waited for ahead of the FMAs.)
+//   * the weights (scalar loads, SGPR operands of the packed FMAs) and the input rows (LDS reads) of
+//     (channel, tz) group g + 1 are issued before group g's FMAs, and the one lgkmcnt(0) of a group
+//     stands before that issue: scalar loads return out of order, so any wait on them is a full drain,
+//     and placed there it only waits for what was issued a whole group of FMAs earlier.
+//   * the outputs leave one step late, behind the next plane's loads, so the wait for those loads at
+//     the LDS store never includes a store of the same step.
+//   * the residual: `add == x` (RES = 2: the ResidualUnit's forward conv(x) + x and its input gradient
+//     dconv(g) + g) is taken from the staged centre plane (channel co, row r + 1, columns w0 + 1 ..),
+//     not loaded again; any other `add` (RES = 1) is loaded behind the plane.
 #ifndef TB_SMALL_ZB
-#define TB_SMALL_ZB 8
+#define TB_SMALL_ZB 0
 #endif
-constexpr int ZB = TB_SMALL_ZB;  // output planes per block
-
-// weights of the z-march as scalar loads from the constant address space (SGPR operands of the packed
-// FMAs) instead of per-FMA-group LDS broadcast reads (TB_SMALL_SW=0: LDS): 320 -> 306 us for the C3
-// 3 -> 3 layer
-#ifndef TB_SMALL_SW
-#define TB_SMALL_SW 1
-#endif
+constexpr int ZB = TB_SMALL_ZB;  // output planes per block; 0: chosen per launch (zplanes below)
+constexpr int NS = 3;            // ring slots: planes z - 1, z, z + 1; plane z + 2 replaces z - 1
 typedef const __attribute__((address_space(4))) float* cfloat_sp;
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef float f2v __attribute__((ext_vector_type(2)));
 
-// U: (channel, tz) groups unrolled per iteration of the z-march's FMA loop (the weights of a group are
-// scalar loads, so a deeper unroll lets more of them be issued ahead; 1 / 3 / 9 measured 280 / 268 / 267 us: 3)
-template <int CI, int CO, bool ADD = false, int U = 1>
+template <int CI, int CO, int RES = 0>
 __global__ __launch_bounds__(NT) void k_conv3d_small_z(const float* __restrict__ x, const float* __restrict__ wt,
                                                        const float* __restrict__ bias, float* __restrict__ y, int D,
-                                                       int H, int W, int XP, int nhb, const float* __restrict__ add) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // [4 slots][CI][ROWS + 2][XP], col 0 = w = -1
-  constexpr int RS = ROWS + 2, NR = CI * RS;                 // staged rows per plane
+                                                       int H, int W, int XP, int nhb, const float* __restrict__ add,
+                                                       int vec, int zb) {
+  static_assert(RES != 2 || CI == CO, "the aliased residual is the input itself");
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [NS slots][CI][ROWS + 2][XP], col 0 = w = -1
+  constexpr int RS = ROWS + 2, NR = CI * RS, NW = NT / 64;   // staged rows per plane, waves
+  constexpr int NJ = NR / NW;                                // staged rows per wave
+  constexpr int NG = CI * 3, GW = CO * 9;                    // (channel, tz) groups; weights per group
+  static_assert(NR % NW == 0, "rows deal evenly to the waves");
   const int slot_f = CI * RS * XP;
-  float* ws = xs + 4 * slot_f;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i < 4 * slot_f; i += NT) xs[i] = 0.f;  // halo columns stay zero (DMA writes 1 .. W)
-  for (int i = tid; i < CO * CI * 27; i += NT) ws[i] = wt[i];
-  const int hb = (int)blockIdx.x % nhb, z0 = ((int)blockIdx.x / nhb) * ZB, n = (int)blockIdx.y;
+  for (int i = tid; i < NS * slot_f / 4; i += NT)  // XP % 4 == 0; halo columns stay zero
+    reinterpret_cast<f4v*>(xs)[i] = f4v{0.f, 0.f, 0.f, 0.f};
+  const int hb = (int)blockIdx.x % nhb, z0 = ((int)blockIdx.x / nhb) * zb, n = (int)blockIdx.y;
   const int h0 = hb * ROWS;
   const int64_t plane = (int64_t)H * W, vol = (int64_t)D * plane;
-  __syncthreads();
-  // stage input plane zi into ring slot (zi - z0 + 1) & 3: in-range rows by DMA, others zeroed
-  auto stage = [&](int zi) {
-    float* sl = xs + ((zi - z0 + 1) & 3) * slot_f;
-    for (int row = wave; row < NR; row += NT / 64) {
-      const int ci = row / RS, r = row - ci * RS, hi = h0 + r - 1;
-      float* dst = sl + row * XP + 1;
-      if (zi >= 0 && zi < D && hi >= 0 && hi < H) {
-        const float* src = x + ((int64_t)n * CI + ci) * vol + (int64_t)zi * plane + (int64_t)hi * W;
+  const int zend = z0 + zb < D ? z0 + zb : D;
+  // plane zi -> registers: row wave + NW j (channel j / 2, staged row wave + NW (j % 2)), columns
+  // lane + 64 sg.  Every address is clamped into the tensor (plane, row and column) and every LDS store
+  // below is unconditional, so no load or wait sits under a branch of its own: a load whose wait the
+  // compiler sees skipped on some path is waited for wherever its register is next reused.
+  static_assert(RS == 2 * NW, "a wave's rows: two per channel");
+  int hoff[2], cof[kSeg], lcol[kSeg];
+  unsigned lm[2][kSeg];  // all ones where (row, column) is inside the tensor
 #pragma unroll
-        for (int sg = 0; sg < kSeg; ++sg) {
-          const int c = lane + 64 * sg;
-          if (c < W) __builtin_amdgcn_global_load_lds((gptr_t)(src + c), (lptr_t)(dst + 64 * sg), 4, 0, 0);
-        }
-      } else {
+  for (int q = 0; q < 2; ++q) {
+    const int hi = h0 + wave + NW * q - 1;
 #pragma unroll
-        for (int sg = 0; sg < kSeg; ++sg) {
-          const int c = lane + 64 * sg;
-          if (c < W) dst[c] = 0.f;
-        }
-      }
+    for (int sg = 0; sg < kSeg; ++sg) lm[q][sg] = ((hi >= 0) & (hi < H) & (lane + 64 * sg < W)) ? ~0u : 0u;
+    hoff[q] = (hi < 0 ? 0 : hi >= H ? H - 1 : hi) * W;  // < H W <= 2^31 / 4 elements (launcher)
+  }
+#pragma unroll
+  for (int sg = 0; sg < kSeg; ++sg) {
+    cof[sg] = lane + 64 * sg < W ? lane + 64 * sg : W - 1;
+    lcol[sg] = lane + 64 * sg < W ? lane + 64 * sg : XP - 2;
+  }
+  const float* xn = x + (int64_t)n * CI * vol;
+  // (a plane past zend is not needed: its loads stay, all at the sample's first element -- one line --
+  // so that no load and no LDS store of the march sits under a branch)
+  auto load = [&](int zi, float (&rg)[NJ][kSeg]) {
+    const bool need = zi <= zend;
+    const float* xz = xn + (need ? (int64_t)(zi < 0 ? 0 : zi >= D ? D - 1 : zi) * plane : 0);
+    const int64_t cv = need ? vol : 0;
+    const int nm = need ? ~0 : 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const float* src = xz + (int64_t)(j >> 1) * cv + (hoff[j & 1] & nm);
+#pragma unroll
+      for (int sg = 0; sg < kSeg; ++sg) rg[j][sg] = src[cof[sg] & nm];
     }
   };
-  stage(z0 - 1);
-  stage(z0);
-  stage(z0 + 1);
-  __builtin_amdgcn_s_waitcnt(0);  // this wave's DMA landed
+  // ... -> ring slot (zi - z0 + 1) % NS, zeros for rows and planes outside the tensor; the lanes past W
+  // write a zero to column XP - 1, which nothing reads (the last thread's 6-wide read ends at W + 4)
+  auto store = [&](int zi, const float (&rg)[NJ][kSeg]) {
+    float* sl = xs + ((zi - z0 + 1) % NS) * slot_f + 1;
+    const unsigned zm = ((zi >= 0) & (zi < D)) ? ~0u : 0u;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      float* dst = sl + (wave + NW * j) * XP;
+#pragma unroll
+      for (int sg = 0; sg < kSeg; ++sg)  // the zero-select as a bit mask: no branch, no wait but the value's own
+        dst[lcol[sg]] = __uint_as_float(__float_as_uint(rg[j][sg]) & lm[j & 1][sg] & zm);
+    }
+  };
+  float ra[NJ][kSeg], rb[NJ][kSeg], rc[NJ][kSeg];
+  __syncthreads();  // zero fill before any plane store
+  load(z0 - 1, ra);
+  load(z0, rb);
+  load(z0 + 1, rc);  // (z0 + 1 may be past D: clamped here, zeroed at the store)
+  store(z0 - 1, ra);
+  store(z0, rb);
+  store(z0 + 1, rc);
   __syncthreads();
   const int tpr = (W + WPT - 1) / WPT;
   const int r = tid / tpr, w0 = (tid - r * tpr) * WPT;
   const bool act = r < ROWS && h0 + r < H;
-  const int zend = z0 + ZB < D ? z0 + ZB : D;
   const int h = h0 + r;
-  // step z: fetch plane z + 2 | store step z - 1's outputs | FMAs of plane z into registers | wait, barrier.
-  // The outputs leave one step late, so the wait for the fetch never waits for the step's own stores
-  // (the residual `add` values are loaded at the start of their step, used a step later).
-  float prev[CO][WPT], padd[CO][WPT];
+  float bv[CO];
+#pragma unroll
+  for (int co = 0; co < CO; ++co) bv[co] = bias ? bias[co] : 0.f;
+  const cfloat_sp wc = (cfloat_sp)wt;
+  // group g = (ci, tz): its CO x 9 weights and the thread's 3 rows of 6 inputs
+  auto issue = [&](int g, int zr, float (&wg)[GW], float (&vg)[3][WPT + 2]) {
+    const int ci = g / 3, tz = g - 3 * ci;
+#pragma unroll
+    for (int co = 0; co < CO; ++co)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) wg[co * 9 + t] = wc[((co * CI + ci) * 3 + tz) * 9 + t];
+    const float* base = xs + ((zr + tz) % NS) * slot_f + (ci * RS + r) * XP + w0;  // column w0 = w0 - 1 + halo
+#pragma unroll
+    for (int ty = 0; ty < 3; ++ty) {
+      // 16-B aligned (XP % 4 == 0, w0 % 4 == 0): one ds_read_b128 + one ds_read_b64, no conflicts
+      const f4v v4 = *reinterpret_cast<const f4v*>(base + ty * XP);
+      const f2v v2 = *reinterpret_cast<const f2v*>(base + ty * XP + 4);
+      vg[ty][0] = v4.x, vg[ty][1] = v4.y, vg[ty][2] = v4.z, vg[ty][3] = v4.w, vg[ty][4] = v2.x, vg[ty][5] = v2.y;
+    }
+  };
+  float prev[CO][WPT];
   auto put = [&](int zp) {
 #pragma unroll
     for (int co = 0; co < CO; ++co) {
-      const int64_t o = ((int64_t)n * CO + co) * vol + (int64_t)zp * plane + (int64_t)h * W + w0;
+      float* o = y + ((int64_t)n * CO + co) * vol + (int64_t)zp * plane + (int64_t)h * W + w0;
+      if (vec) {  // W % 4 == 0 and y 16-B aligned
+        *reinterpret_cast<f4v*>(o) = f4v{prev[co][0], prev[co][1], prev[co][2], prev[co][3]};
+      } else {
 #pragma unroll
-      for (int k = 0; k < WPT; ++k)
-        if (w0 + k < W) y[o + k] = ADD ? prev[co][k] + padd[co][k] : prev[co][k];
+        for (int k = 0; k < WPT; ++k)
+          if (w0 + k < W) o[k] = prev[co][k];
+      }
     }
   };
+  // step z: load plane z + 2 | (RES 1: load the residual) | store step z - 1's outputs | FMAs of plane z |
+  // barrier | LDS store of plane z + 2 over plane z - 1 | barrier
   for (int z = z0; z < zend; ++z) {
-    if (z + 2 < zend + 1) stage(z + 2);  // the next plane's fetch overlaps this plane's FMAs
+    load(z + 2, ra);
     if (act) {
-      if (z > z0) put(z - 1);
-      if (ADD) {
+      float res[CO][WPT];
+      if (RES == 1) {
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
-          const int64_t o = ((int64_t)n * CO + co) * vol + (int64_t)z * plane + (int64_t)h * W + w0;
+          const float* s = add + ((int64_t)n * CO + co) * vol + (int64_t)z * plane + (int64_t)h * W + w0;
 #pragma unroll
-          for (int k = 0; k < WPT; ++k) padd[co][k] = w0 + k < W ? add[o + k] : 0.f;
+          for (int k = 0; k < WPT; ++k) res[co][k] = s[w0 + k < W ? k : 0];  // columns past W are not stored
         }
       }
+      if (z > z0) put(z - 1);
       float acc[CO][WPT];
 #pragma unroll
-      for (int co = 0; co < CO; ++co) {
-        const float b = bias ? bias[co] : 0.f;
+      for (int co = 0; co < CO; ++co)
 #pragma unroll
-        for (int k = 0; k < WPT; ++k) acc[co][k] = b;
-      }
-#pragma unroll U
-      for (int ct = 0; ct < CI * 3; ++ct) {
-        const int ci = ct / 3, tz = ct - 3 * ci;
-        const float* base = xs + ((z - z0 + tz) & 3) * slot_f + (ci * RS + r) * XP + w0;
+        for (int k = 0; k < WPT; ++k) acc[co][k] = bv[co];
+      float wg[2][GW], vg[2][3][WPT + 2];
+      issue(0, z - z0, wg[0], vg[0]);
 #pragma unroll
-        for (int ty = 0; ty < 3; ++ty) {
-          const float* src = base + ty * XP;
-          const float4 v4 = *reinterpret_cast<const float4*>(src);
-          const float2 v2 = *reinterpret_cast<const float2*>(src + 4);
-          const float v[WPT + 2] = {v4.x, v4.y, v4.z, v4.w, v2.x, v2.y};
+      for (int g = 0; g < NG; ++g) {
+        const int ci = g / 3, tz = g - 3 * ci;
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): group g's operands, issued a group ago
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < NG) issue(g + 1, z - z0, wg[(g + 1) & 1], vg[(g + 1) & 1]);  // (no load past the last group)
+        __builtin_amdgcn_sched_barrier(0);
+        const float(&w)[GW] = wg[g & 1];
+        const float(&v)[3][WPT + 2] = vg[g & 1];
 #pragma unroll
-          for (int co = 0; co < CO; ++co) {
+        for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
-            for (int tx = 0; tx < 3; ++tx) {
-              const int wi = (((co * CI + ci) * 3 + tz) * 3 + ty) * 3 + tx;
-              const float wv = TB_SMALL_SW ? ((cfloat_sp)wt)[wi] : ws[wi];
+          for (int co = 0; co < CO; ++co)
 #pragma unroll
-              for (int k = 0; k < WPT; ++k) acc[co][k] = fmaf(wv, v[k + tx], acc[co][k]);
-            }
-          }
+            for (int tx = 0; tx < 3; ++tx)
+#pragma unroll
+              for (int k = 0; k < WPT; ++k) acc[co][k] = fmaf(w[co * 9 + ty * 3 + tx], v[ty][k + tx], acc[co][k]);
+        if (RES == 2 && tz == 1) {  // the centre plane's row r + 1, columns w0 + 1 ..: x[ci] at the outputs
+#pragma unroll
+          for (int k = 0; k < WPT; ++k) res[ci < CO ? ci : 0][k] = v[1][k + 1];
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
       for (int co = 0; co < CO; ++co)
 #pragma unroll
-        for (int k = 0; k < WPT; ++k) prev[co][k] = acc[co][k];
+        for (int k = 0; k < WPT; ++k) prev[co][k] = RES ? acc[co][k] + res[co][k] : acc[co][k];
     }
-    __builtin_amdgcn_s_waitcnt(0);  // plane z + 2 landed (this wave's share; the stores were issued a step ago)
-    __syncthreads();                // ... and every wave's; slot of z - 1 free for plane z + 3
+    __syncthreads();  // every wave is done with plane z - 1
+    store(z + 2, ra);
+    __syncthreads();
   }
-  if (act && zend > z0) put(zend - 1);
+  if (act) put(zend - 1);
 }
 
 __global__ __launch_bounds__(256) void k_add_inplace(float* __restrict__ y, const float* __restrict__ a, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] += a[i];
+}
+
+// Output planes per block of the z-march: `base` blocks per z segment, `per_cu` blocks resident per CU.
+// A block of l planes takes about l + 2 plane steps (its first three planes arrive together); the
+// segments run in rounds of per_cu x CUs blocks, and the fewest steps over all rounds win (C3: 27 planes,
+// 720 blocks in one round of 768; the fixed 8 planes were 2400 blocks in four rounds).  No segment is
+// shorter than 8 planes (or D): a block reads l + 2 planes for l, and the model does not count traffic.
+int zplanes(int D, int base, int per_cu) {
+  const int slots = (per_cu < 1 ? 1 : per_cu) * tb::num_cu();
+  int best = 1 << 30, zl = D;
+  for (int l = D; l >= (D < 8 ? D : 8); --l) {
+    const int zs = (D + l - 1) / l, rounds = (base * zs + slots - 1) / slots, cost = rounds * (l + 2);
+    if (cost < best) best = cost, zl = l;
+  }
+  return zl;
 }
 
 template <int CI, int CO>
@@ -251,15 +335,21 @@ int launch(const float* x, const float* w, const float* b, const float* add, flo
            hipStream_t st) {
   const int XP = (W + 2 + WPT + 3) / 4 * 4;  // halo, slack for the last thread's 6-wide read, 16-B rows
   const size_t lds = sizeof(float) * ((size_t)CI * 3 * (ROWS + 2) * XP + CO * CI * 27);
-  if ((W + WPT - 1) / WPT * ROWS > NT || lds > 65536 || XP > 64 * kSeg) return TB_ERR_UNSUPPORTED_SIZE;
+  if ((W + WPT - 1) / WPT * ROWS > NT || lds > 65536 || XP > 64 * kSeg || (int64_t)H * W > (1 << 29))
+    return TB_ERR_UNSUPPORTED_SIZE;
   const int nhb = (H + ROWS - 1) / ROWS;
-  const size_t lds_z = sizeof(float) * ((size_t)4 * CI * (ROWS + 2) * XP + CO * CI * 27);
-  if (lds_z <= 65536 * 2) {  // z-march (3 (channel, tz) groups per FMA-loop iteration)
-    void (*kern)(const float*, const float*, const float*, float*, int, int, int, int, int, const float*) =
-        add ? k_conv3d_small_z<CI, CO, true, 3> : k_conv3d_small_z<CI, CO, false, 3>;
+  const size_t lds_z = sizeof(float) * ((size_t)NS * CI * (ROWS + 2) * XP);
+  if (lds_z <= 65536 * 2) {  // z-march
+    void (*kern)(const float*, const float*, const float*, float*, int, int, int, int, int, const float*, int, int) =
+        k_conv3d_small_z<CI, CO, 0>;
+    if (add) kern = k_conv3d_small_z<CI, CO, 1>;
+    if constexpr (CI == CO)
+      if (add == x) kern = k_conv3d_small_z<CI, CO, 2>;  // conv(x) + x: the residual is the staged input
     if (tb::allow_full_lds(kern) != hipSuccess) return TB_ERR_HIP;  // once per kernel (kernels.h)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nhb * ((D + ZB - 1) / ZB)), (unsigned)N), dim3(NT), lds_z, st, x, w, b, y,
-                       D, H, W, XP, nhb, add);
+    const int vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;  // 16-byte output stores
+    const int zb = ZB ? ZB : zplanes(D, N * nhb, (int)(163840 / lds_z));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nhb * ((D + zb - 1) / zb)), (unsigned)N), dim3(NT), lds_z, st, x, w, b, y,
+                       D, H, W, XP, nhb, add, vec, zb);
     return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
   }
   hipLaunchKernelGGL((k_conv3d_small<CI, CO>), dim3((unsigned)(nhb * D), (unsigned)N), dim3(NT), lds, st, x, w, b, y,

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "num_cu.h"
 #include "texbias.h"
@@ -34,6 +35,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // first version of these kernels was LDS-bound at 8 % of the FMA rate).
 typedef const __attribute__((address_space(4))) float* cfloat_p;
 typedef const __attribute__((address_space(4))) f2v* cf2v_p;
+
+// f(integral_constant<int, i>) for i = B .. N - 1: a loop that cannot stay rolled
+template <int B, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < N) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, N>(f);
+  }
+}
 
 // ------------------------------------------------------------------------------ stride-2 conv
 struct S2Args {
@@ -153,21 +163,48 @@ __global__ __launch_bounds__(NTH) void k_conv_s2_fewin(S2Args a) {
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx) v[c * 27 + tz * 9 + ty * 3 + tx] = sl[(c * NR + ty) * PX + tx];
       }
-      const cf2v_p kp = (cf2v_p)(cfloat_p)a.K;
+      // The thread's weights are one contiguous stream of NP = MP x CIN 27 pairs (pair-major over its output
+      // pairs).  It goes through two SGPR buffers of BT pairs: lgkmcnt(0), then the NEXT batch's scalar loads,
+      // then this batch's FMAs -- scalar loads return out of order, so a wait on them is always a full drain,
+      // and placed here it only waits for loads issued a whole batch of FMAs earlier.  The last batch loads
+      // only the pairs that exist.
+      constexpr int KC = CIN * 27, NP = MP * KC, BT = 16, NB = (NP + BT - 1) / BT;
+      const cf2v_p kp = (cf2v_p)(cfloat_p)a.K + mh * NP;
+      f2v kb[2][BT];
+      auto kload = [&](int b, f2v (&k)[BT]) {
 #pragma unroll
-      for (int mm = 0; mm < MP; ++mm) {
-        const int m = mh * MP + mm;
-        f2v acc = bias2[mm];
+        for (int i = 0; i < BT; ++i)
+          if (b * BT + i < NP) k[i] = kp[b * BT + i];
+      };
+      kload(0, kb[0]);
+      f2v acc = bias2[0];
+      // (a compile-time loop: `#pragma unroll` gives up on NB batches of this size, and v[] goes to scratch)
+      static_for<0, NB>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) (the first: the position's LDS reads as well)
+        __builtin_amdgcn_sched_barrier(0);
+        if (b + 1 < NB) kload(b + 1, kb[(b + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 0; k < CIN * 27; ++k) acc = __builtin_elementwise_fma(f2v{v[k], v[k]}, kp[m * CIN * 27 + k], acc);
-        if (LATE) {
-          pend[mm] = acc;
-        } else {
-          float* o = outb + (int64_t)z * oplane;
-          o[(int64_t)(2 * m) * a.Do * oplane] = acc.x;
-          o[(int64_t)(2 * m + 1) * a.Do * oplane] = acc.y;
+        for (int i = 0; i < BT; ++i) {
+          const int p = b * BT + i, mm = p / KC, k = p - mm * KC;
+          if (p < NP) {
+            if (k == 0) acc = bias2[mm];
+            acc = __builtin_elementwise_fma(f2v{v[k], v[k]}, kb[b & 1][i], acc);
+            if (k == KC - 1) {
+              if (LATE) {
+                pend[mm] = acc;
+              } else {
+                const int m = mh * MP + mm;
+                float* o = outb + (int64_t)z * oplane;
+                o[(int64_t)(2 * m) * a.Do * oplane] = acc.x;
+                o[(int64_t)(2 * m + 1) * a.Do * oplane] = acc.y;
+              }
+            }
+          }
         }
-      }
+      });
     }
     __syncthreads();  // every wave is done with this step's slots before the next step's stores
   }
