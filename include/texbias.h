@@ -57,6 +57,19 @@ extern "C" {
                          coefficient (c, kh, kw, kd) (UNSHIFTED) is kept iff u > f[0] = p, with
                          u = (splitmix64(idx ^ l) >> 40) / 2^24, idx = ((c H + kh) i[1] + kw) i[2] + kd,
                          i[1] = W, i[2] = D, l = splitmix64(seed) (host); applied as (m(f) + m(-f)) / 2 */
+#define TB_OP_MASK 7  /* the caller's own real k-space mask: l = DEVICE address of a contiguous float32
+                         M[Cm][H][W][D] in the CENTRED layout of fftshift(fftn(x)) (what disk_mask and the
+                         users of Fourier.shift_fourier build, filters_and_operators.py:136-197, 594-632):
+                         element (s_h, s_w, s_d) multiplies the coefficient of unshifted frequency
+                         k_a = (s_a - n_a/2) mod n_a (integer division).  i[0] = Cm: 1 = one mask for all
+                         channels, C = one per channel; i[1] = W, i[2] = D as for ZF.
+                         y = Re(IFFT(ifftshift(M . fftshift(FFT x)))): each stored coefficient is scaled by
+                         (M[s(f)] + M[s(-f)]) / 2, exact for a real M.  The launch functions return
+                         TB_ERR_INVALID_ARG before launching anything when l = 0, i[1..2] != the plan's
+                         (W, D) or i[0] is neither 1 nor C.  The kernels read M when they run (no copy is
+                         taken): the caller keeps it alive until the launch has run on `stream`; values
+                         written to it in stream order before the launch, or between replays of a captured
+                         graph, apply */
 
 #define TB_MAX_OPS 6
 #define TB_MAX_BATCH 8 /* samples per launch group; larger batches are split by the library */

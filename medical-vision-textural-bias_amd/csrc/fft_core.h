@@ -640,6 +640,16 @@ TB_HD float zf_keep(const tb_op& op, uint64_t idx) {
   return u > op.f[0] ? 1.f : 0.f;
 }
 
+// TB_OP_MASK: a float mask M[Cm][H][W][D] in device memory, in the layout of fftshift(fftn(x)) -- what
+// disk_mask (filters_and_operators.py:136-197) and the users of Fourier.shift_fourier (:594-632) build.
+// Element offset of the unshifted coefficient (kh, kw, kd); `ch` = channel * H, or 0 for a shared mask.
+// 64-bit: a per-channel mask of a 4 x 240 x 240 x 155 sample is 35.7 M floats, larger ones pass 2^31.
+TB_HD int64_t mask_index(int64_t ch, int kh, int kw, int kd, int H, int W, int D) {
+  return ((ch + shifted(kh, H)) * W + shifted(kw, W)) * (int64_t)D + shifted(kd, D);
+}
+// y = Re(IFFT(ifftshift(M . fftshift(FFT x)))): the .real symmetrises, exact for a real M
+TB_HD float mask_factor(float mf, float mn) { return 0.5f * (mf + mn); }
+
 // Apply a sample's op program to one stored half-spectrum coefficient.
 // Every op is followed by the reference's `.real` (G4: Hermitian symmetrisation);
 // on a half spectrum that is exact for symmetric masks, needs (M(f)+M(-f))/2 for
@@ -699,6 +709,13 @@ TB_HD cf apply_ops(const SO& so, int chan, cf v, const FreqCol& fc, int kh, int 
         const float m = 0.5f * (zf_keep(op, ((ch + (uint64_t)kh) * Wz + (uint64_t)fc.kw) * Dz + (uint64_t)fc.kd) +
                                 zf_keep(op, ((ch + (uint64_t)h.nk) * Wz + (uint64_t)fc.nkw) * Dz + (uint64_t)fc.nkd));
         v = scl(v, m);
+      } break;
+      case TB_OP_MASK: {  // the caller's mask, read at the fftshift-ed positions of f and -f
+        const float* M = reinterpret_cast<const float*>(op.l);
+        const int Wm = op.i[1], Dm = op.i[2];
+        const int64_t ch = op.i[0] > 1 ? (int64_t)chan * H : 0;
+        v = scl(v, mask_factor(M[mask_index(ch, kh, fc.kw, fc.kd, H, Wm, Dm)],
+                               M[mask_index(ch, h.nk, fc.nkw, fc.nkd, H, Wm, Dm)]));
       } break;
       default: break;
     }

@@ -111,6 +111,20 @@ TB_HD void ops_bfly(const SO& so, int chan, v2* v, const FreqCol& fc, int kh0, i
           v[q] = m * v[q];
         }
       } break;
+      case TB_OP_MASK: {  // the butterfly's 2 R mask values are requested before the first is used
+        const float* M = reinterpret_cast<const float*>(op.l);
+        const int Wm = op.i[1], Dm = op.i[2];
+        const int64_t ch = op.i[0] > 1 ? (int64_t)chan * H : 0;
+        float mf[R], mn[R];
+        TB_UNROLL
+        for (int q = 0; q < R; ++q) {
+          const int kh = kh0 + kst * q;
+          mf[q] = M[mask_index(ch, kh, fc.kw, fc.kd, H, Wm, Dm)];
+          mn[q] = M[mask_index(ch, negk(kh, H), fc.nkw, fc.nkd, H, Wm, Dm)];
+        }
+        TB_UNROLL
+        for (int q = 0; q < R; ++q) v[q] = mask_factor(mf[q], mn[q]) * v[q];
+      } break;
       default: break;
     }
   }

@@ -941,6 +941,17 @@ static int run_copy(const tb_plan* p, const float* x, const int64_t* xs, float* 
   return TB_OK;
 }
 
+// TB_OP_MASK ops carry a device address the kernels dereference: checked here, before any launch
+static bool mask_ops_ok(const tb_plan* p, const tb_sample_ops* ops, int B, int C) {
+  for (int b = 0; b < B; ++b)
+    for (int o = 0; o < ops[b].n && o < TB_MAX_OPS; ++o) {
+      const tb_op& op = ops[b].op[o];
+      if (op.kind != TB_OP_MASK) continue;
+      if (op.l == 0 || op.i[1] != p->dev.W || op.i[2] != p->dev.D || (op.i[0] != 1 && op.i[0] != C)) return false;
+    }
+  return true;
+}
+
 template <int RA, int RB>
 static int kspace_filter(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
                          void* ws, size_t ws_bytes, int B, int C, const tb_sample_ops* ops, uint32_t* minmax,
@@ -949,6 +960,7 @@ static int kspace_filter(const tb_plan* p, const float* x, const int64_t* xs, fl
   if (ws_bytes < tb_workspace_bytes(p, B * C) || !ws) return TB_ERR_WORKSPACE;
   for (int b = 0; b < B; ++b)
     if (ops[b].n < 0 || ops[b].n > TB_MAX_OPS) return TB_ERR_INVALID_ARG;
+  if (!mask_ops_ok(p, ops, B, C)) return TB_ERR_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // Runs of consecutive samples with the same route, in launch groups of <= TB_MAX_BATCH samples
   // (the op programs travel in the kernel arguments): empty programs are copied through (the
@@ -1021,6 +1033,7 @@ static int kspace_stats(const tb_plan* p, const float* x, const int64_t* xs, voi
                              int C, const tb_sample_ops* ops, double* out, void* stream) {
   if (!p || !x || !xs || !ops || !out || B < 1 || C < 1) return TB_ERR_INVALID_ARG;
   if (ws_bytes < tb_workspace_bytes(p, B * C) || !ws) return TB_ERR_WORKSPACE;
+  if (!mask_ops_ok(p, ops, B, C)) return TB_ERR_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   cf* S = static_cast<cf*>(ws);
   const int H = p->dev.H, W = p->dev.W, D = p->dev.D;

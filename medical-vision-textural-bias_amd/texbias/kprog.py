@@ -22,7 +22,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import (TB_MAX_OPS, TB_OP_DISK, TB_OP_GIBBS, TB_OP_LAYER, TB_OP_SPIKE, TB_OP_WRAP, TB_OP_ZF, TbOp)
+from ._abi import (TB_MAX_OPS, TB_OP_DISK, TB_OP_GIBBS, TB_OP_LAYER, TB_OP_MASK, TB_OP_SPIKE, TB_OP_WRAP, TB_OP_ZF,
+                   TbOp)
 
 
 @dataclass(frozen=True)
@@ -174,6 +175,24 @@ def zf_op(p: float, seed: int, spatial3: Sequence[int]) -> TbOp:
     op.i[1], op.i[2] = int(spatial3[1]), int(spatial3[2])
     k = splitmix64(int(seed) & _M64)
     op.l = k - (1 << 64) if k >= (1 << 63) else k   # int64 field, same bits
+    return op
+
+
+# --------------------------------------------------------------------- mask
+def mask_op(mask_ptr: int, mask_channels: int, hwd: Sequence[int], chan: int = -1) -> TbOp:
+    """The caller's own real k-space mask (TB_OP_MASK in include/texbias.h): ``mask_ptr`` is the device
+    address of a contiguous float32 ``M[mask_channels][H][W][D]`` in the layout of ``fftshift(fftn(x))``
+    (Fourier.shift_fourier, filters_and_operators.py:594-632); ``mask_channels`` is 1 for a mask shared
+    by all channels, else the image's channel count; ``hwd`` the (H, W, D) geometry of the transform.
+    The kernels read the buffer when they run: keep it alive until then."""
+    if not mask_ptr:
+        raise ValueError("mask_op needs the device address of the mask")
+    if int(mask_channels) < 1:
+        raise ValueError(f"mask_channels must be 1 or the channel count, got {mask_channels}")
+    op = _op(TB_OP_MASK, chan)
+    op.l = int(mask_ptr)
+    op.i[0] = int(mask_channels)
+    op.i[1], op.i[2] = int(hwd[1]), int(hwd[2])
     return op
 
 

@@ -1,0 +1,96 @@
+"""User-supplied k-space masks as transforms (TB_OP_MASK).
+
+The reference's notebooks build a mask by hand and multiply it into ``Fourier.shift_fourier(x)``
+(filters_and_operators.py:594-632): an annulus, an anisotropic low-pass, a Hann window, Cartesian line
+undersampling.  ``KSpaceMask`` / ``KSpaceMaskd`` run such a mask through the same fused
+forward-FFT -> op program -> inverse-FFT round trip as the drop-in filters, with no spectrum stored,
+and compose with them in a ``pipeline.FusedChain``.  These classes are additions of this package; the
+drop-in modules keep exactly the reference's names.
+
+The mask is real, laid out like ``fftshift(fftn(x))`` over the spatial axes: shape ``spatial`` (shared
+by every channel) or ``(C,) + spatial``.  It lives on the device: a numpy array or CPU tensor is copied
+there once at first use, a HIP tensor is used in place, so later writes to it take effect.
+"""
+from __future__ import annotations
+
+from typing import Dict, Hashable, List, Mapping, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import kprog as K
+from . import runtime as rt
+from .transform_base import MapTransform, Transform
+
+
+class KSpaceMask(Transform):
+    """y = Re(IFFT(ifftshift(mask * fftshift(FFT(img))))) for an image [C, *spatial]."""
+
+    def __init__(self, mask) -> None:
+        m = torch.as_tensor(mask)
+        if m.is_complex():
+            raise ValueError("KSpaceMask: complex masks are not supported")
+        if m.requires_grad:
+            raise ValueError("KSpaceMask: a mask with requires_grad is not supported")
+        self.mask = m.to(torch.float32).contiguous()
+        self._dev: Dict[torch.device, torch.Tensor] = {}
+
+    def mask_on(self, device: Optional[torch.device] = None) -> torch.Tensor:
+        """The float32 contiguous mask on ``device`` (default: the current HIP device)."""
+        if self.mask.device.type == "cuda" and (device is None or device == self.mask.device):
+            return self.mask
+        if device is None:
+            if torch.utils.data.get_worker_info() is not None:
+                raise rt.TexbiasError("KSpaceMask cannot run inside a (forked) DataLoader worker: apply it to the "
+                                      "collated batch (texbias.pipeline.FusedChain)")
+            if not torch.cuda.is_available():
+                raise rt.TexbiasError("KSpaceMask needs a HIP device (there is no CPU implementation)")
+            device = torch.device("cuda", torch.cuda.current_device())
+        m = self._dev.get(device)
+        if m is None:
+            m = self.mask.to(device).contiguous()
+            self._dev[device] = m
+        return m
+
+    def program(self, spatial: Sequence[int], channels: int, device: Optional[torch.device] = None) -> List:
+        """The op program for images [channels, *spatial] (as the drop-in filters' ``program``)."""
+        spatial = tuple(int(s) for s in spatial)
+        if tuple(self.mask.shape) == spatial:
+            cm = 1
+        elif tuple(self.mask.shape) == (int(channels),) + spatial:
+            cm = int(channels)
+        else:
+            raise ValueError(f"KSpaceMask: mask shape {tuple(self.mask.shape)} is neither {spatial} nor "
+                             f"{(int(channels),) + spatial}")
+        return [K.mask_op(self.mask_on(device).data_ptr(), cm, K.geometry(spatial).hwd)]
+
+    def __call__(self, img):
+        x = torch.Tensor(img) if isinstance(img, np.ndarray) else img
+        if x.dim() < 2:
+            raise ValueError("KSpaceMask expects an image [C, *spatial]")
+        dev = x.device if x.device.type == "cuda" else None
+        m = self.mask_on(dev)
+        xd = x.to(device=m.device, dtype=torch.float32)
+        n_dims = xd.dim() - 1
+        y = torch.ops.texbias.kspace_mask(xd, m, n_dims, xd.shape[0], 0)
+        return y if x.device == m.device else y.to(x.device)
+
+
+class KSpaceMaskd(MapTransform):
+    """Dictionary version of :class:`KSpaceMask`."""
+
+    def __init__(self, keys, mask, allow_missing_keys: bool = False) -> None:
+        MapTransform.__init__(self, keys, allow_missing_keys)
+        self.transform = KSpaceMask(mask)
+
+    def program(self, spatial: Sequence[int], channels: int, device: Optional[torch.device] = None) -> List:
+        return self.transform.program(spatial, channels, device)
+
+    def __call__(self, data: Mapping[Hashable, torch.Tensor]):
+        d = dict(data)
+        for key in self.key_iterator(d):
+            d[key] = self.transform(d[key])
+        return d
+
+
+__all__ = ["KSpaceMask", "KSpaceMaskd"]

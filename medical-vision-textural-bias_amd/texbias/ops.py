@@ -102,6 +102,37 @@ def kspace_filter_programs(x: torch.Tensor, n_dims: int, programs: Sequence[Sequ
     return torch.ops.texbias.kspace_filter(x, n_dims, pack_programs(programs), channels, pad)
 
 
+@torch.library.custom_op("texbias::kspace_mask", mutates_args=())
+def kspace_mask(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: int, pad: int = 0) -> torch.Tensor:
+    """y = Re(IFFT(ifftshift(mask * fftshift(FFT(x))))) over the trailing ``n_dims`` axes of
+    [B*channels..., *spatial] (last axis padded by ``pad`` zero columns) with the caller's real mask,
+    laid out like ``Fourier.shift_fourier(x, n_dims)``: ``spatial`` or ``(channels,) + spatial``, float32,
+    contiguous, on x's device.  One fused pass; the kernel reads ``mask`` on the current stream."""
+    return rt.kspace_mask(x, mask, n_dims, pad=pad, channels=channels)
+
+
+@kspace_mask.register_fake
+def _kspace_mask_fake(x, mask, n_dims, channels, pad=0):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+
+
+def _kspace_mask_setup(ctx, inputs, output):
+    x, mask, n_dims, channels, pad = inputs
+    if mask.requires_grad:
+        raise ValueError("texbias::kspace_mask has no gradient w.r.t. the mask (a learnable mask is not supported)")
+    ctx.save_for_backward(mask)
+    ctx.n_dims, ctx.channels, ctx.d = n_dims, channels, x.shape[-1]
+
+
+def _kspace_mask_backward(ctx, gy):
+    # the symmetrised real mask makes x -> y self-adjoint; the zero pad columns take no gradient
+    (mask,) = ctx.saved_tensors
+    return torch.ops.texbias.kspace_mask(gy[..., : ctx.d], mask, ctx.n_dims, ctx.channels, 0), None, None, None, None
+
+
+kspace_mask.register_autograd(_kspace_mask_backward, setup_context=_kspace_mask_setup)
+
+
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
     B = img.shape[0]
     n_dims = img.dim() - 1

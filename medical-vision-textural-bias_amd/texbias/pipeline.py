@@ -31,7 +31,8 @@ def _kind(t) -> str:
 
 
 KSPACE = {"RandFourierDiskMaskd", "RandPlaneWaves_ellipsoid", "WrapArtifactd", "WrapArtifact", "GibbsNoise",
-          "RandGibbsNoise", "RandGibbsNoised", "KSpaceSpikeNoise", "RandKSpaceSpikeNoise", "RandKSpaceSpikeNoised"}
+          "RandGibbsNoise", "RandGibbsNoised", "KSpaceSpikeNoise", "RandKSpaceSpikeNoise", "RandKSpaceSpikeNoised",
+          "KSpaceMask", "KSpaceMaskd"}
 POINTWISE = {"SaltAndPepper"}
 CHANNEL = {"SelectChanneld", "MultimodalSlicesd"}
 
@@ -98,6 +99,7 @@ class FusedChain:
         self._mm_b = 0
         self._last_mm: Optional[torch.Tensor] = None
         self._label_sel: List[Optional[int]] = []
+        self._dev: Optional[torch.device] = None   # device of the batch being planned (user masks live there)
 
     @property
     def last_minmax(self) -> Optional[np.ndarray]:
@@ -159,6 +161,9 @@ class FusedChain:
                         t.transforms[kk].set_random_state(t.common_seed)
                 if self.key in t.keys and t._do_transform:
                     prog += spike_program(t.transforms[self.key], c_cur, spatial)
+            elif k in ("KSpaceMask", "KSpaceMaskd"):
+                if k == "KSpaceMask" or self.key in t.keys:   # texbias.masks: the user's own mask, read on the device
+                    prog += t.program(spatial, c_cur, self._dev)
             elif k == "SaltAndPepper":
                 t.randomize(None)
                 close()
@@ -207,6 +212,7 @@ class FusedChain:
         if x.dim() != 5:
             raise ValueError("FusedChain expects [B, C, H, W, D]")
         B, C = x.shape[:2]
+        self._dev = x.device
         plans = plans if plans is not None else self.plan(B, tuple(x.shape[2:]), phases, C)
         return self.execute(x, plans, pad=pad, u=u, cls=cls, seed=seed, out=out)
 
@@ -216,6 +222,7 @@ class FusedChain:
         d = dict(data)
         x = d[self.key]
         keys = [k for k in d]
+        self._dev = x.device if isinstance(x, torch.Tensor) and x.device.type == "cuda" else None
         plans = self.plan(x.shape[0], tuple(x.shape[2:]), kw.pop("phases", None), x.shape[1], keys)
         d[self.key] = self.__call__(x, pad=pad, plans=plans, **kw)
         if "label" in d and any(s is not None for s in self._label_sel):

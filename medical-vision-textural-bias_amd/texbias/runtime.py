@@ -17,7 +17,7 @@ import torch
 
 from ._abi import TB_MAX_BATCH, TB_MAX_OPS, programs_array
 from ._lib import TexbiasError, check, lib
-from .kprog import Geometry, geometry, split_program
+from .kprog import Geometry, geometry, mask_op, split_program
 
 _plans: Dict[Tuple[int, int, int, int], "Plan"] = {}
 _ws: "OrderedDict[Tuple[int, int], torch.Tensor]" = OrderedDict()
@@ -231,6 +231,57 @@ def _kspace_filter_pass(x: torch.Tensor, n_dims: int, programs: Sequence[Sequenc
         check(getattr(lib(), entry)(plan.handle, x.data_ptr(), xs, out.data_ptr(), ys, pad, ws.data_ptr(),
                                     ws.numel(), B, channels, C.addressof(progs), mm_ptr, _stream(x.device)), entry)
     return out
+
+
+def mask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Optional[int] = None) -> Tuple[int, int]:
+    """Host-side check of a user k-space mask against the image ``x`` [*lead, *spatial]: returns
+    (mask channels, image channels).  The mask is ``spatial`` (shared by every channel) or
+    ``(C,) + spatial`` with C = ``channels`` (default: the image's last leading axis); float32,
+    contiguous, on the image's device -- the kernels index it as M[Cm][H][W][D] with no copy, so
+    nothing else is accepted."""
+    if not isinstance(x, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise ValueError("kspace_mask: image and mask must be torch tensors")
+    if n_dims < 1 or x.dim() < n_dims:
+        raise ValueError(f"kspace_mask: {n_dims} transformed axes on a {x.dim()}-d image")
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    lead = x.shape[: x.dim() - n_dims]
+    if channels is None:
+        channels = int(lead[-1]) if len(lead) else 1
+    channels = int(channels)
+    if channels < 1 or (int(np.prod(lead)) if len(lead) else 1) % channels:
+        raise ValueError(f"kspace_mask: {channels} channels do not divide the leading axes {tuple(lead)}")
+    if tuple(mask.shape) == spatial:
+        cm = 1
+    elif tuple(mask.shape) == (channels,) + spatial:
+        cm = channels
+    else:
+        raise ValueError(f"kspace_mask: mask shape {tuple(mask.shape)} is neither {spatial} nor "
+                         f"{(channels,) + spatial}")
+    if mask.dtype != torch.float32:
+        raise ValueError(f"kspace_mask: the mask must be float32, got {mask.dtype}")
+    if not mask.is_contiguous():
+        raise ValueError("kspace_mask: the mask must be contiguous")
+    if mask.device != x.device:
+        raise ValueError(f"kspace_mask: mask on {mask.device}, image on {x.device}")
+    if mask.requires_grad:
+        raise ValueError("kspace_mask: a mask with requires_grad is not supported (no gradient w.r.t. the mask)")
+    return cm, channels
+
+
+def kspace_mask(x: torch.Tensor, mask: torch.Tensor, n_dims: int, pad: int = 0,
+                out: Optional[torch.Tensor] = None, channels: Optional[int] = None) -> torch.Tensor:
+    """y = Re(IFFT(ifftshift(mask * fftshift(FFT(x))))) over the trailing ``n_dims`` axes in one fused
+    round trip (TB_OP_MASK): ``mask`` is laid out like ``Fourier.shift_fourier(x, n_dims)``, shape
+    ``spatial`` or ``(C,) + spatial`` (see ``mask_geometry``).  ``pad`` / ``out`` as ``kspace_filter``;
+    ``out`` may be ``x``; ``channels``: see ``mask_geometry``.  The launch reads ``mask`` on the current
+    stream, with no host sync."""
+    cm, channels = mask_geometry(x, mask, n_dims, channels)
+    require_hip(x, "kspace_mask")
+    hwd = geometry(x.shape[x.dim() - n_dims:]).hwd
+    lead = x.shape[: x.dim() - n_dims]
+    bc = int(np.prod(lead)) if len(lead) else 1
+    prog = [mask_op(mask.data_ptr(), cm, hwd)]
+    return _kspace_filter_pass(x, n_dims, [prog] * (bc // channels), channels, out, pad)
 
 
 def minmax_buffer(device: torch.device, B: int) -> torch.Tensor:
