@@ -69,7 +69,7 @@ extern "C" {
                          (W, D) or i[0] is neither 1 nor C.  The kernels read M when they run (no copy is
                          taken): the caller keeps it alive until the launch has run on `stream`; values
                          written to it in stream order before the launch, or between replays of a captured
-                         graph, apply */
+                         graph, apply.  The gradient of y with respect to M: tb_kspace_mask_grad_f32 below */
 
 #define TB_MAX_OPS 6
 #define TB_MAX_BATCH 8 /* samples per launch group; larger batches are split by the library */
@@ -167,6 +167,26 @@ int tb_disk_mask_f32(float* mask, int64_t outer, int n0, int n1, int n2, int int
  */
 int tb_kspace_logabs_sum_f32(const tb_plan* plan, const float* x, const int64_t* xs, void* ws, size_t ws_bytes,
                              int B, int C, const tb_sample_ops* ops, double* out, void* stream);
+
+/*
+ * Gradient of the TB_OP_MASK round trip y = Re(IFFT(ifftshift(M . fftshift(FFT x)))) with respect to the real
+ * mask M, for an upstream gradient g = dL/dy (real, the image's shape):
+ *   dM[s(f)] = sum Re( X(f) conj(G(f)) ) / (H W D),   X = FFT(x), G = FFT(g)
+ * summed over the B samples, and over the C channels too when Cm = 1 (one mask shared by every channel);
+ * Cm = C gives one gradient per channel.  Every element of the centred layout is an independent variable.
+ *   x, xs : the image, indexed as in tb_kspace_filter_f32
+ *   g, gs : the upstream gradient, same indexing with its own strides (a view without the pad columns works)
+ *   dM    : device, contiguous float32 [Cm][H][W][D] in the centred layout of TB_OP_MASK; overwritten
+ *           completely (no need to zero it), every element written exactly once per launch group with no
+ *           atomics, so the result is bit-reproducible from run to run
+ *   ws    : device workspace of >= tb_mask_grad_workspace_bytes(plan, B*C) bytes: the two forward spectra
+ * Two forward passes A (x, g) and one per-coefficient pass; no inverse transform, nothing is allocated, no
+ * host sync, launches on `stream` only (graph-capturable).  TB_ERR_INVALID_ARG for a null pointer, B < 1,
+ * C < 1 or Cm other than 1 or C; TB_ERR_WORKSPACE for a missing or short workspace; both before any launch.
+ */
+size_t tb_mask_grad_workspace_bytes(const tb_plan* plan, int bc);
+int tb_kspace_mask_grad_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                            float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream);
 
 /*
  * Weight gradient of a 3x3x3 Conv3d / ConvTranspose3d (stride 1 or 2, padding `pad`), f32:

@@ -166,6 +166,44 @@ __global__ __launch_bounds__(NT_GEN) void k_gen_store(GenArgs) {
   if (a.mm) block_minmax_atomic<NT_GEN>(lo, hi, red, a.mm + 2 * (bc / a.C));
 }
 
+// Mask gradient on the full spectra X = S, G = Sg ([nbc][H][W][D], natural order): per (mask channel
+// slot, coefficient with kd <= D/2) the sum over the launch group's volumes of Re(X conj G), scaled by
+// 1 / N, to the centred position of f and, when kd is not self-conjugate (kd = 0, kd = D/2 with D even),
+// of -f -- the write-once rule of maskgrad.h: one thread and one write per element of dM, f and -f
+// bit-equal.
+struct GenMaskGradArgs {
+  const cf* S;
+  const cf* Sg;
+  float* dM;
+  int H, W, D, C, nb, Cm, accumulate;
+  float scale;
+};
+__global__ __launch_bounds__(NT_GEN) void k_gen_maskgrad(GenMaskGradArgs a) {
+  const int H = a.H, W = a.W, D = a.D, Dh = D / 2 + 1;
+  const int64_t n = (int64_t)H * W * D, nh = (int64_t)H * W * Dh;
+  const int slot = (int)blockIdx.y;
+  const int nv = a.Cm == 1 ? a.nb * a.C : a.nb;
+  const int Dtop = (D % 2 == 0) ? D / 2 : -1;
+  for (int64_t e = (int64_t)blockIdx.x * NT_GEN + threadIdx.x; e < nh; e += (int64_t)gridDim.x * NT_GEN) {
+    const int64_t hw = e / Dh;
+    const int kd = (int)(e - hw * Dh), kh = (int)(hw / W), kw = (int)(hw - (int64_t)kh * W);
+    const int64_t src = hw * D + kd;
+    float acc = 0.f;
+    for (int k = 0; k < nv; ++k) {
+      const int64_t vol = a.Cm == 1 ? k : (int64_t)k * a.C + slot;
+      const cf x = a.S[vol * n + src], g = a.Sg[vol * n + src];
+      acc += x.x * g.x + x.y * g.y;
+    }
+    const float v = acc * a.scale;
+    float* p = a.dM + mask_index((int64_t)slot * H, kh, kw, kd, H, W, D);
+    *p = a.accumulate ? *p + v : v;
+    if (kd != 0 && kd != Dtop) {
+      float* q = a.dM + mask_index((int64_t)slot * H, negk(kh, H), negk(kw, W), D - kd, H, W, D);
+      *q = a.accumulate ? *q + v : v;
+    }
+  }
+}
+
 unsigned gen_blocks(int64_t n) {
   const int64_t b = (n + NT_GEN * 4 - 1) / (NT_GEN * 4);
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -254,6 +292,32 @@ hipError_t launch_gen_logabs(const GenLaunch& g, double* out, hipStream_t st) {
   if (e != hipSuccess) return e;
   a.S = g.S + (int64_t)a.nbc * n;
   hipLaunchKernelGGL(k_gen_logabs, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, a);
+  return hipGetLastError();
+}
+
+// buffers b0, b1, b2 of nbc H W D coefficients: x transforms in (b1, b2) and leaves X in b2, g then
+// transforms in (b0, b1) and leaves G in b1
+size_t gen_maskgrad_workspace_bytes(int H, int W, int D, int bc) { return (size_t)3 * bc * H * W * D * sizeof(cf); }
+
+hipError_t launch_gen_spectrum(const GenLaunch& g, hipStream_t st) {
+  GenArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.pl = g.pl;
+  a.x = g.x;
+  a.xsbc = g.xs[0]; a.xsh = g.xs[1]; a.xsw = g.xs[2];
+  a.S = g.S;
+  a.bc0 = g.bc0;
+  a.C = g.C;
+  a.nbc = g.nbc;
+  return gen_forward(a, st);
+}
+
+hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, float* dM, int C, int nb, int Cm,
+                               int accumulate, hipStream_t st) {
+  const int64_t n = (int64_t)pl.H * pl.W * pl.D;
+  const GenMaskGradArgs m{X, G, dM, pl.H, pl.W, pl.D, C, nb, Cm, accumulate,
+                          (float)(1.0 / ((double)pl.H * (double)pl.W * (double)pl.D))};
+  hipLaunchKernelGGL(k_gen_maskgrad, dim3(gen_blocks(n / 2 + 1), Cm), dim3(NT_GEN), 0, st, m);
   return hipGetLastError();
 }
 

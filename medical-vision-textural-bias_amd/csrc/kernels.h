@@ -12,6 +12,7 @@
 #include <unordered_map>
 
 #include "fft_core.h"
+#include "maskgrad.h"
 #include "sap_core.h"
 
 namespace tb {
@@ -67,6 +68,8 @@ template <int RS> hipError_t launch_slab_fwd(const SlabFwdArgs& a, dim3 grid, si
 template <int RS> hipError_t launch_kspace(const KspaceArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_slab_inv(const SlabInvArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_kspace_stats(const StatsArgs& a, dim3 grid, size_t lds, hipStream_t st);
+// mask gradient (maskgrad.h, kern_maskgrad.hip): grid = (tiles of a.T columns, mask channel slots)
+template <int RS> hipError_t launch_kspace_maskgrad(const MaskGradArgs& a, dim3 grid, size_t lds, hipStream_t st);
 
 // Compile-time slab plans (slab_ct.h, kern_slab_ct.hip): persistent passes A / C, grid from ncu.
 bool slab_ct_supported(int W, int D);
@@ -101,6 +104,15 @@ struct GenLaunch {
 size_t gen_workspace_bytes(int H, int W, int D, int bc);
 hipError_t launch_gen_filter(const GenLaunch& g, hipStream_t st);
 hipError_t launch_gen_logabs(const GenLaunch& g, double* out, hipStream_t st);
+// Mask gradient on the fallback.  launch_gen_spectrum: forward DFT of g.x's volumes, scratch in g.S and
+// the spectrum left in g.S + nbc H W D.  Three buffers b0, b1, b2 of nbc H W D coefficients
+// (gen_maskgrad_workspace_bytes) hold both spectra: x transforms in (b1, b2) and leaves X in b2, the
+// upstream gradient then transforms in (b0, b1) and leaves G in b1.  launch_gen_maskgrad: one
+// element-wise k_gen_maskgrad over the full spectra of the group's nb samples.
+size_t gen_maskgrad_workspace_bytes(int H, int W, int D, int bc);
+hipError_t launch_gen_spectrum(const GenLaunch& g, hipStream_t st);
+hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, float* dM, int C, int nb, int Cm,
+                               int accumulate, hipStream_t st);
 
 #if defined(__HIPCC__)
 struct DevCtx {

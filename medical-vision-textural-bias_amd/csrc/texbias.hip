@@ -1066,6 +1066,93 @@ static int kspace_stats(const tb_plan* p, const float* x, const int64_t* xs, voi
   return TB_OK;
 }
 
+// ------------------------------------------------------------ mask gradient (maskgrad.h)
+// Tile of the mask-gradient pass: half of pass B's width (the x and g tiles share one pass-B tile of
+// LDS), narrowed until a workgroup's register slots hold its coefficients.
+static int maskgrad_tile(const tb_plan* p) {
+  int T = pick_tile(p->dev.H, p->lds_max) / 2;
+  if (T < 1) T = 1;
+  while (T > 1 && p->dev.H * T > MG_MAX_TILE) --T;
+  return T;
+}
+// The element-wise fallback also takes a plan whose single column exceeds the register slots or the
+// LDS, and one whose volume offsets pass 32 bits.
+static bool maskgrad_generic(const tb_plan* p) {
+  const int H = p->dev.H;
+  return p->generic || H > MG_MAX_TILE || (size_t)tile_geo(H, 2).total_cf * sizeof(cf) > (size_t)p->lds_max ||
+         (int64_t)H * p->dev.W * (p->dev.D / 2 + 1) >= (1LL << 31);
+}
+
+size_t tb_mask_grad_workspace_bytes(const tb_plan* plan, int bc) {
+  if (!plan || bc < 0) return 0;
+  const int H = plan->dev.H, W = plan->dev.W, D = plan->dev.D;
+  if (maskgrad_generic(plan)) return gen_maskgrad_workspace_bytes(H, W, D, bc);
+  return (size_t)2 * bc * H * W * (D / 2 + 1) * sizeof(cf);
+}
+
+template <int RA, int RB>
+static int kspace_mask_grad(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                            float* dM, int Cm, void* ws, int B, int C, hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  const double scale = 1.0 / ((double)H * (double)W * (double)D);
+  if (maskgrad_generic(p)) {
+    for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+      const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+      const double vox = (double)nb * C * H * W * D;
+      cf* b0p = static_cast<cf*>(ws);
+      cf* b1p = b0p + (size_t)nb * C * H * W * D;
+      cf* b2p = b1p + (size_t)nb * C * H * W * D;
+      {
+        // per voxel: 4 B read and 8 B written by the load, 16 B per axis; twice
+        Timer t(0, st, 2.0 * vox * 60.0, "k_gen_dft");
+        const GenLaunch gx{p->dev, x, xs, nullptr, nullptr, b1p, 0, b0 * C, C, nb * C, nullptr, nullptr};
+        TB_HIP(tb::launch_gen_spectrum(gx, st));
+        const GenLaunch gg{p->dev, g, gs, nullptr, nullptr, b0p, 0, b0 * C, C, nb * C, nullptr, nullptr};
+        TB_HIP(tb::launch_gen_spectrum(gg, st));
+      }
+      {
+        Timer t(1, st, 2.0 * (double)nb * C * H * W * Dh * 8.0 + (double)Cm * H * W * D * 4.0, "k_gen_maskgrad");
+        TB_HIP(tb::launch_gen_maskgrad(p->dev, b2p, b1p, dM, C, nb, Cm, b0 > 0 ? 1 : 0, st));
+      }
+    }
+    return TB_OK;
+  }
+  const int T = maskgrad_tile(p);
+  const int ntiles = (W * Dh + T - 1) / T;
+  const size_t lds = (size_t)tile_geo(H, 2 * T).total_cf * sizeof(cf);
+  cf* Sx = static_cast<cf*>(ws);
+  cf* Sg = Sx + (size_t)B * C * H * W * Dh;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const double vox = (double)nb * C * H * W * D, spec = (double)nb * C * H * W * Dh * 8.0;
+    {
+      Timer t(0, st, 2.0 * (vox * 4.0 + spec), use_ct_slab(p) ? "k_slab_fwd_ct16" : "k_slab_fwd");
+      int rc = launch_slab_fwd<RA>(p, x, xs, Sx, b0 * C, nb * C, st);
+      if (rc) return rc;
+      rc = launch_slab_fwd<RA>(p, g, gs, Sg, b0 * C, nb * C, st);
+      if (rc) return rc;
+    }
+    {
+      Timer t(1, st, 2.0 * spec + (double)Cm * H * W * D * 4.0, "k_kspace_maskgrad");
+      const MaskGradArgs ma{p->dev, Sx, Sg, dM, b0 * C, C, nb, Cm, T, b0 > 0 ? 1 : 0, (float)scale};
+      TB_HIP(launch_kspace_maskgrad<RB>(ma, dim3(ntiles, Cm), lds, st));
+    }
+  }
+  return TB_OK;
+}
+
+int tb_kspace_mask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                            float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+  if (!p || !x || !xs || !g || !gs || !dM || B < 1 || C < 1 || (Cm != 1 && Cm != C)) return TB_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < tb_mask_grad_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define TB_ARGS p, x, xs, g, gs, dM, Cm, ws, B, C, st
+  if (p->rset_wd == RS_SMALL)
+    return p->rset_h == RS_SMALL ? kspace_mask_grad<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_mask_grad<RS_SMALL, RS_ALL>(TB_ARGS);
+  return p->rset_h == RS_SMALL ? kspace_mask_grad<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_mask_grad<RS_ALL, RS_ALL>(TB_ARGS);
+#undef TB_ARGS
+}
+
 int tb_kspace_filter_f32(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
                          void* ws, size_t ws_bytes, int B, int C, const tb_sample_ops* ops, uint32_t* minmax,
                          void* stream) {

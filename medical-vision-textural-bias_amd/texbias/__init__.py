@@ -5,7 +5,8 @@ Layering (DESIGN.md):
   _lib / runtime     libtexbias.so loader, plans, workspaces, batched launches (HIP only)
   shell              plane-wave ellipsoid shell candidates
   transform_base     MONAI-0.5 transform protocol (MONAI's own classes when installed)
-  masks              user-supplied k-space masks as transforms (KSpaceMask, KSpaceMaskd)
+  masks              user-supplied k-space masks as transforms (KSpaceMask, KSpaceMaskd) and as a
+                     trainable module (LearnedKSpaceMask)
   pipeline           batched device-side augmentation stage (fused chain) for training
   unet / losses      MONAI-equivalent 3-D residual U-Net and DiceLoss (PyTorch-ROCm)
   train              train step, DDP over RCCL

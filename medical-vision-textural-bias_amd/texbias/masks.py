@@ -4,8 +4,9 @@ The reference's notebooks build a mask by hand and multiply it into ``Fourier.sh
 (filters_and_operators.py:594-632): an annulus, an anisotropic low-pass, a Hann window, Cartesian line
 undersampling.  ``KSpaceMask`` / ``KSpaceMaskd`` run such a mask through the same fused
 forward-FFT -> op program -> inverse-FFT round trip as the drop-in filters, with no spectrum stored,
-and compose with them in a ``pipeline.FusedChain``.  These classes are additions of this package; the
-drop-in modules keep exactly the reference's names.
+and compose with them in a ``pipeline.FusedChain``.  ``LearnedKSpaceMask`` is the trainable form: an
+``nn.Module`` whose mask is a parameter with a gradient (``torch.ops.texbias.kspace_mask_learn``).  These
+classes are additions of this package; the drop-in modules keep exactly the reference's names.
 
 The mask is real, laid out like ``fftshift(fftn(x))`` over the spatial axes: shape ``spatial`` (shared
 by every channel) or ``(C,) + spatial``.  It lives on the device: a numpy array or CPU tensor is copied
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from . import kprog as K
+from . import ops as _ops  # noqa: F401 - registers torch.ops.texbias.*
 from . import runtime as rt
 from .transform_base import MapTransform, Transform
 
@@ -93,4 +95,42 @@ class KSpaceMaskd(MapTransform):
         return d
 
 
-__all__ = ["KSpaceMask", "KSpaceMaskd"]
+class LearnedKSpaceMask(torch.nn.Module):
+    """A trainable real k-space mask: y = Re(IFFT(ifftshift(mask * fftshift(FFT(x))))) for a batch
+    ``x`` [B, C, *spatial], with autograd with respect to ``x`` and to ``mask`` (every element of the
+    centred layout is an independent parameter).  ``init``: array or tensor of shape ``spatial`` (shared
+    by every channel) or ``(C,) + spatial``; held as the float32 contiguous ``nn.Parameter`` ``mask``."""
+
+    def __init__(self, init, n_dims: int = 3) -> None:
+        super().__init__()
+        m = torch.as_tensor(init)
+        if m.is_complex():
+            raise ValueError("LearnedKSpaceMask: complex masks are not supported")
+        n_dims = int(n_dims)
+        if n_dims < 1 or m.dim() not in (n_dims, n_dims + 1):
+            raise ValueError(f"LearnedKSpaceMask: init of shape {tuple(m.shape)} is neither spatial nor (C,) + spatial "
+                             f"for {n_dims} transformed axes")
+        self.n_dims = n_dims
+        self.mask = torch.nn.Parameter(m.detach().to(torch.float32).contiguous().clone())
+
+    def forward(self, x: torch.Tensor, pad: int = 0) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.dim() != self.n_dims + 2:
+            raise ValueError(f"LearnedKSpaceMask expects a batch [B, C, *spatial] with {self.n_dims} spatial axes")
+        if x.dtype != torch.float32:
+            raise ValueError(f"LearnedKSpaceMask: float32 images expected, got {x.dtype}")
+        spatial, channels = tuple(x.shape[2:]), int(x.shape[1])
+        if tuple(self.mask.shape) not in (spatial, (channels,) + spatial):
+            raise ValueError(f"LearnedKSpaceMask: mask shape {tuple(self.mask.shape)} is neither {spatial} nor "
+                             f"{(channels,) + spatial}")
+        if x.device.type != "cuda":
+            raise rt.TexbiasError("LearnedKSpaceMask needs a HIP device (there is no CPU implementation)")
+        return torch.ops.texbias.kspace_mask_learn(x, self.mask, self.n_dims, channels, pad)
+
+    def as_transform(self) -> KSpaceMask:
+        """A :class:`KSpaceMask` over ``self.mask.detach()``, e.g. for a ``pipeline.FusedChain`` at
+        inference.  It shares the parameter's storage, so later optimizer steps show through; after
+        moving the module to another device, take a new one."""
+        return KSpaceMask(self.mask.detach())
+
+
+__all__ = ["KSpaceMask", "KSpaceMaskd", "LearnedKSpaceMask"]

@@ -12,6 +12,11 @@ Reference interfaces each op replaces (file:line under the reference root):
                              source_code/filters_and_operators.py:236-252, 370-393, 503-515,
                              663-705, 906-983; stylization_layers.py:79-116
   texbias::salt_and_pepper_  SaltAndPepper.salt_and_pepper  filters_and_operators.py:465-482
+  texbias::kspace_mask       a hand-built mask multiplied into Fourier.shift_fourier(x)  :594-632
+  texbias::kspace_mask_learn the same with the mask as a trainable tensor (autograd w.r.t. image and mask;
+                             the reference's only trainable k-space object has d/d alpha = 0 and its
+                             drivers update it by finite differences, Gibbs_GD)
+  texbias::kspace_mask_grad  the mask gradient on its own
   texbias::gibbs_layer       GibbsNoiseLayer.forward / _apply_mask  stylization_layers.py:79-116
                              (autograd: the filter is self-adjoint; d/d alpha = 0 as in the reference)
 """
@@ -131,6 +136,59 @@ def _kspace_mask_backward(ctx, gy):
 
 
 kspace_mask.register_autograd(_kspace_mask_backward, setup_context=_kspace_mask_setup)
+
+
+@torch.library.custom_op("texbias::kspace_mask_grad", mutates_args=())
+def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, channels: int, mask_channels: int) -> torch.Tensor:
+    """Gradient of ``kspace_mask(x, M)`` with respect to the mask for the upstream gradient ``g`` (the
+    image's shape, any strides with a contiguous last axis): ``spatial`` for ``mask_channels`` = 1 (summed
+    over the channels), else ``(channels,) + spatial``; summed over the samples.  No autograd formula
+    (double backward is not supported)."""
+    return rt.kspace_mask_grad(x, g, n_dims, mask_channels, channels)
+
+
+@kspace_mask_grad.register_fake
+def _kspace_mask_grad_fake(x, g, n_dims, channels, mask_channels):
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    return x.new_empty(spatial if mask_channels == 1 else (mask_channels,) + spatial)
+
+
+@torch.library.custom_op("texbias::kspace_mask_learn", mutates_args=())
+def kspace_mask_learn(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: int, pad: int = 0) -> torch.Tensor:
+    """``texbias::kspace_mask`` (the same fused pass, bit for bit) for a learnable mask: autograd with
+    respect to the image and to the mask.  Every element of the mask's centred layout is an independent
+    variable."""
+    return rt.kspace_mask_learn(x, mask, n_dims, pad=pad, channels=channels)
+
+
+@kspace_mask_learn.register_fake
+def _kspace_mask_learn_fake(x, mask, n_dims, channels, pad=0):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+
+
+def _kspace_mask_learn_setup(ctx, inputs, output):
+    x, mask, n_dims, channels, pad = inputs
+    ctx.save_for_backward(x, mask)
+    ctx.n_dims, ctx.channels, ctx.d = n_dims, channels, x.shape[-1]
+    ctx.cm = 1 if mask.dim() == n_dims else channels
+
+
+@torch.autograd.function.once_differentiable
+def _kspace_mask_learn_backward(ctx, gy):
+    # image: the filter is self-adjoint; mask: Re(X conj G) / N per coefficient; the zero pad columns
+    # take no gradient, and the view without them is read in place.  Once differentiable: a double
+    # backward raises instead of dropping the mask's share of the second derivative.
+    x, mask = ctx.saved_tensors
+    g = gy[..., : ctx.d]
+    gx = gm = None
+    if ctx.needs_input_grad[0]:
+        gx = torch.ops.texbias.kspace_mask(g, mask.detach(), ctx.n_dims, ctx.channels, 0)
+    if ctx.needs_input_grad[1]:
+        gm = torch.ops.texbias.kspace_mask_grad(x, g, ctx.n_dims, ctx.channels, ctx.cm)
+    return gx, gm, None, None, None
+
+
+kspace_mask_learn.register_autograd(_kspace_mask_learn_backward, setup_context=_kspace_mask_learn_setup)
 
 
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

@@ -233,12 +233,14 @@ def _kspace_filter_pass(x: torch.Tensor, n_dims: int, programs: Sequence[Sequenc
     return out
 
 
-def mask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Optional[int] = None) -> Tuple[int, int]:
+def mask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Optional[int] = None,
+                  learnable: bool = False) -> Tuple[int, int]:
     """Host-side check of a user k-space mask against the image ``x`` [*lead, *spatial]: returns
     (mask channels, image channels).  The mask is ``spatial`` (shared by every channel) or
     ``(C,) + spatial`` with C = ``channels`` (default: the image's last leading axis); float32,
     contiguous, on the image's device -- the kernels index it as M[Cm][H][W][D] with no copy, so
-    nothing else is accepted."""
+    nothing else is accepted.  A mask with ``requires_grad`` passes only with ``learnable`` (the
+    ``kspace_mask_learn`` path, which has the gradient with respect to the mask)."""
     if not isinstance(x, torch.Tensor) or not isinstance(mask, torch.Tensor):
         raise ValueError("kspace_mask: image and mask must be torch tensors")
     if n_dims < 1 or x.dim() < n_dims:
@@ -263,7 +265,7 @@ def mask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Op
         raise ValueError("kspace_mask: the mask must be contiguous")
     if mask.device != x.device:
         raise ValueError(f"kspace_mask: mask on {mask.device}, image on {x.device}")
-    if mask.requires_grad:
+    if mask.requires_grad and not learnable:
         raise ValueError("kspace_mask: a mask with requires_grad is not supported (no gradient w.r.t. the mask)")
     return cm, channels
 
@@ -275,13 +277,85 @@ def kspace_mask(x: torch.Tensor, mask: torch.Tensor, n_dims: int, pad: int = 0,
     ``spatial`` or ``(C,) + spatial`` (see ``mask_geometry``).  ``pad`` / ``out`` as ``kspace_filter``;
     ``out`` may be ``x``; ``channels``: see ``mask_geometry``.  The launch reads ``mask`` on the current
     stream, with no host sync."""
-    cm, channels = mask_geometry(x, mask, n_dims, channels)
+    return _kspace_mask(x, mask, n_dims, pad, out, channels, False)
+
+
+def kspace_mask_learn(x: torch.Tensor, mask: torch.Tensor, n_dims: int, pad: int = 0,
+                      channels: Optional[int] = None) -> torch.Tensor:
+    """``kspace_mask`` for a mask that may require grad (the forward of ``torch.ops.texbias.kspace_mask_learn``;
+    the gradient with respect to the mask is ``kspace_mask_grad``)."""
+    return _kspace_mask(x, mask, n_dims, pad, None, channels, True)
+
+
+def _kspace_mask(x, mask, n_dims, pad, out, channels, learnable):
+    cm, channels = mask_geometry(x, mask, n_dims, channels, learnable)
     require_hip(x, "kspace_mask")
     hwd = geometry(x.shape[x.dim() - n_dims:]).hwd
     lead = x.shape[: x.dim() - n_dims]
     bc = int(np.prod(lead)) if len(lead) else 1
     prog = [mask_op(mask.data_ptr(), cm, hwd)]
     return _kspace_filter_pass(x, n_dims, [prog] * (bc // channels), channels, out, pad)
+
+
+def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channels: int,
+                     channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``kspace_mask(x, M)`` with respect to the mask for an upstream gradient ``g`` (the
+    image's shape): dM[s(f)] = sum Re(FFT(x)(f) conj(FFT(g)(f))) / N in the mask's centred layout, summed
+    over the samples and, with ``mask_channels`` = 1, over the channels.  Returns ``spatial`` for
+    ``mask_channels`` = 1, else ``(C,) + spatial`` with C = ``channels`` (default: the image's last
+    leading axis).  ``x`` and ``g`` may have any strides with a contiguous last axis (``gy[..., :D]`` of
+    a padded output is read in place).  Two forward passes and one per-coefficient pass on the current
+    stream (``tb_kspace_mask_grad_f32``); every element is written once, so repeated calls agree bit
+    for bit.  ``out``: a float32 contiguous tensor of the result's shape on the image's device to
+    overwrite (it need not be zeroed)."""
+    if not isinstance(x, torch.Tensor) or not isinstance(g, torch.Tensor):
+        raise ValueError("kspace_mask_grad: image and upstream gradient must be torch tensors")
+    if n_dims < 1 or x.dim() < n_dims:
+        raise ValueError(f"kspace_mask_grad: {n_dims} transformed axes on a {x.dim()}-d image")
+    if tuple(g.shape) != tuple(x.shape):
+        raise ValueError(f"kspace_mask_grad: upstream gradient {tuple(g.shape)} does not match the image {tuple(x.shape)}")
+    if x.dtype != torch.float32 or g.dtype != torch.float32:
+        raise ValueError(f"kspace_mask_grad: float32 tensors expected, got {x.dtype} and {g.dtype}")
+    if g.device != x.device:
+        raise ValueError(f"kspace_mask_grad: upstream gradient on {g.device}, image on {x.device}")
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    lead = x.shape[: x.dim() - n_dims]
+    if channels is None:
+        channels = int(lead[-1]) if len(lead) else 1
+    channels, cm = int(channels), int(mask_channels)
+    bc = int(np.prod(lead)) if len(lead) else 1
+    if channels < 1 or bc % channels:
+        raise ValueError(f"kspace_mask_grad: {channels} channels do not divide the leading axes {tuple(lead)}")
+    if cm != 1 and cm != channels:
+        raise ValueError(f"kspace_mask_grad: {cm} mask channels for {channels} image channels (1 or {channels})")
+    require_hip(x, "kspace_mask_grad")
+    geo = geometry(spatial)
+    H, W, D = geo.hwd
+
+    def strided(t):
+        v = _bc_view(t, n_dims)
+        if v is None or _hwd_strides(geo, v[3])[2] != 1:
+            t = t.contiguous()
+            v = _bc_view(t, n_dims)
+        return t, (C.c_int64 * 3)(v[1], *_hwd_strides(geo, v[3])[:2])
+
+    x, xs = strided(x)
+    g, gs = strided(g)
+    shape = spatial if cm == 1 else (cm,) + spatial
+    if out is None:
+        dm = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        dm = out
+        if (not isinstance(dm, torch.Tensor) or tuple(dm.shape) != shape or dm.dtype != torch.float32
+                or not dm.is_contiguous() or dm.device != x.device):
+            raise ValueError(f"kspace_mask_grad: out must be a float32 contiguous {shape} tensor on {x.device}")
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_mask_grad_workspace_bytes(plan.handle, bc)))
+        check(lib().tb_kspace_mask_grad_f32(plan.handle, x.data_ptr(), xs, g.data_ptr(), gs, dm.data_ptr(), cm,
+                                            ws.data_ptr(), ws.numel(), bc // channels, channels, _stream(x.device)),
+              "tb_kspace_mask_grad_f32")
+    return dm
 
 
 def minmax_buffer(device: torch.device, B: int) -> torch.Tensor:
