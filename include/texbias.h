@@ -189,6 +189,29 @@ int tb_kspace_mask_grad_f32(const tb_plan* plan, const float* x, const int64_t* 
                             float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream);
 
 /*
+ * The centred complex spectrum itself (Fourier.shift_fourier / inv_shift_fourier,
+ * source_code/filters_and_operators.py:594-632), two linear maps, each the other's adjoint up to N = H W D:
+ *   export  K = fftshift(fftn(x))             x real float32, K complex64
+ *   import  y = Re(ifftn(ifftshift(K)))       any complex64 K (it need not be Hermitian): the reference's
+ *                                             `.real`, exact as the inverse of K_s(f) = (K(f) + conj(K(-f))) / 2
+ *   x, xs : the image, indexed as in tb_kspace_filter_f32 (any strides, contiguous last axis)
+ *   y, ys : the output image, likewise; y_pad zero columns are written after D
+ *   K     : device, contiguous complex64 [B*C][H][W][D] (interleaved re, im) in the centred layout of
+ *           TB_OP_MASK.  The export overwrites it completely (no need to zero it): every element is written
+ *           exactly once with no atomics, f and -f from one value, so the result is bit-reproducible
+ *   ws    : device workspace of >= tb_spectrum_workspace_bytes(plan, B*C) bytes: the half spectrum
+ * Export: forward pass A and one per-coefficient pass; import: one per-coefficient pass and the inverse
+ * pass C.  Nothing is allocated, no host sync, launches on `stream` only (graph-capturable).
+ * TB_ERR_INVALID_ARG for a null pointer, B < 1, C < 1 or y_pad < 0; TB_ERR_WORKSPACE for a missing or short
+ * workspace; both before any launch.
+ */
+size_t tb_spectrum_workspace_bytes(const tb_plan* plan, int bc);
+int tb_kspace_export_f32(const tb_plan* plan, const float* x, const int64_t* xs, void* K /* complex64 [bc][H][W][D] */,
+                         void* ws, size_t ws_bytes, int B, int C, void* stream);
+int tb_kspace_import_f32(const tb_plan* plan, const void* K, float* y, const int64_t* ys, int y_pad, void* ws,
+                         size_t ws_bytes, int B, int C, void* stream);
+
+/*
  * Weight gradient of a 3x3x3 Conv3d / ConvTranspose3d (stride 1 or 2, padding `pad`), f32:
  *   dW[m][c][tz][ty][tx] = sum_n,z,y,x G[n][m][z][y][x] * X[n][c][s z+tz-pad][s y+ty-pad][s x+tx-pad]
  * G [N][M][Do][Ho][Wo] and X [N][Cc][Di][Hi][Wi] contiguous (device); dW [M][Cc][27] (device,

@@ -204,6 +204,42 @@ __global__ __launch_bounds__(NT_GEN) void k_gen_maskgrad(GenMaskGradArgs a) {
   }
 }
 
+// Centred spectrum K[bc][H][W][D] (spectrum.h) and the full natural-order spectrum S[nbc][H][W][D].
+// Export: per coefficient with kd <= D/2, S(f) to the centred position of f and, when kd is not
+// self-conjugate, its conjugate to the position of -f: one thread and one write per element of K.
+// Import: a shifted gather, S(f) = K[s(f)]; k_gen_store's real part symmetrises.
+struct GenSpectrumArgs {
+  cf* S;
+  cf* K;
+  int H, W, D, bc0;
+};
+__global__ __launch_bounds__(NT_GEN) void k_gen_export(GenSpectrumArgs a) {
+  const int H = a.H, W = a.W, D = a.D, Dh = D / 2 + 1;
+  const int64_t n = (int64_t)H * W * D, nh = (int64_t)H * W * Dh;
+  const int bcl = (int)blockIdx.y;
+  const cf* Sb = a.S + (int64_t)bcl * n;
+  cf* Kb = a.K + (int64_t)(a.bc0 + bcl) * n;
+  for (int64_t e = (int64_t)blockIdx.x * NT_GEN + threadIdx.x; e < nh; e += (int64_t)gridDim.x * NT_GEN) {
+    const int64_t hw = e / Dh;
+    const int kd = (int)(e - hw * Dh), kh = (int)(hw / W), kw = (int)(hw - (int64_t)kh * W);
+    const cf v = Sb[hw * D + kd];
+    Kb[mask_index(0, kh, kw, kd, H, W, D)] = v;
+    if (kd != 0 && 2 * kd != D) Kb[mask_index(0, negk(kh, H), negk(kw, W), D - kd, H, W, D)] = conj(v);
+  }
+}
+__global__ __launch_bounds__(NT_GEN) void k_gen_import(GenSpectrumArgs a) {
+  const int H = a.H, W = a.W, D = a.D;
+  const int64_t n = (int64_t)H * W * D;
+  const int bcl = (int)blockIdx.y;
+  cf* Sb = a.S + (int64_t)bcl * n;
+  const cf* Kb = a.K + (int64_t)(a.bc0 + bcl) * n;
+  for (int64_t e = (int64_t)blockIdx.x * NT_GEN + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT_GEN) {
+    const int64_t hw = e / D;
+    const int kd = (int)(e - hw * D), kh = (int)(hw / W), kw = (int)(hw - (int64_t)kh * W);
+    Sb[e] = Kb[mask_index(0, kh, kw, kd, H, W, D)];
+  }
+}
+
 unsigned gen_blocks(int64_t n) {
   const int64_t b = (n + NT_GEN * 4 - 1) / (NT_GEN * 4);
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -318,6 +354,40 @@ hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, 
   const GenMaskGradArgs m{X, G, dM, pl.H, pl.W, pl.D, C, nb, Cm, accumulate,
                           (float)(1.0 / ((double)pl.H * (double)pl.W * (double)pl.D))};
   hipLaunchKernelGGL(k_gen_maskgrad, dim3(gen_blocks(n / 2 + 1), Cm), dim3(NT_GEN), 0, st, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_export(const GenLaunch& g, cf* K, hipStream_t st) {
+  const int64_t n = (int64_t)g.pl.H * g.pl.W * g.pl.D;
+  const GenSpectrumArgs m{g.S + (int64_t)g.nbc * n, K, g.pl.H, g.pl.W, g.pl.D, g.bc0};
+  hipLaunchKernelGGL(k_gen_export, dim3(gen_blocks(n / 2 + 1), g.nbc), dim3(NT_GEN), 0, st, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_import(const GenLaunch& g, const cf* K, hipStream_t st) {
+  GenArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.pl = g.pl;
+  a.y = g.y;
+  a.ysbc = g.ys[0]; a.ysh = g.ys[1]; a.ysw = g.ys[2];
+  a.ypad = g.ypad;
+  a.bc0 = g.bc0;
+  a.C = g.C;
+  a.nbc = g.nbc;
+  a.scale = (float)(1.0 / ((double)g.pl.H * (double)g.pl.W * (double)g.pl.D));
+  const int H = a.pl.H, W = a.pl.W, D = a.pl.D;
+  const int64_t n = (int64_t)H * W * D;
+  cf* S0 = g.S;
+  cf* S1 = g.S + (int64_t)a.nbc * n;
+  const GenSpectrumArgs m{S1, const_cast<cf*>(K), H, W, D, g.bc0};
+  hipLaunchKernelGGL(k_gen_import, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, m);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = gen_axis(S1, S0, a.pl.tw[0], H, a.nbc, (int64_t)W * D, true, st);
+  if (e == hipSuccess) e = gen_axis(S0, S1, a.pl.tw[1], W, (int64_t)a.nbc * H, D, true, st);
+  if (e == hipSuccess) e = gen_axis(S1, S0, a.pl.tw[2], D, (int64_t)a.nbc * H * W, 1, true, st);
+  if (e != hipSuccess) return e;
+  a.S = S0;
+  hipLaunchKernelGGL(k_gen_store, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, a);
   return hipGetLastError();
 }
 

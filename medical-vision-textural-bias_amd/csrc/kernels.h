@@ -14,6 +14,7 @@
 #include "fft_core.h"
 #include "maskgrad.h"
 #include "sap_core.h"
+#include "spectrum.h"
 
 namespace tb {
 
@@ -70,6 +71,9 @@ template <int RS> hipError_t launch_slab_inv(const SlabInvArgs& a, dim3 grid, si
 template <int RS> hipError_t launch_kspace_stats(const StatsArgs& a, dim3 grid, size_t lds, hipStream_t st);
 // mask gradient (maskgrad.h, kern_maskgrad.hip): grid = (tiles of a.T columns, mask channel slots)
 template <int RS> hipError_t launch_kspace_maskgrad(const MaskGradArgs& a, dim3 grid, size_t lds, hipStream_t st);
+// centred spectrum export / import (spectrum.h, kern_spectrum.hip): grid = (tiles of a.T columns, volumes)
+template <int RS> hipError_t launch_kspace_export(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
+template <int RS> hipError_t launch_kspace_import(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
 
 // Compile-time slab plans (slab_ct.h, kern_slab_ct.hip): persistent passes A / C, grid from ncu.
 bool slab_ct_supported(int W, int D);
@@ -113,6 +117,12 @@ size_t gen_maskgrad_workspace_bytes(int H, int W, int D, int bc);
 hipError_t launch_gen_spectrum(const GenLaunch& g, hipStream_t st);
 hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, float* dM, int C, int nb, int Cm,
                                int accumulate, hipStream_t st);
+// Centred spectrum on the fallback, in the two buffers of gen_workspace_bytes.  launch_gen_export: after
+// launch_gen_spectrum(g), a shifted copy of the spectrum's kd <= D/2 half into K[bc][H][W][D] with the
+// write-once rule of spectrum.h.  launch_gen_import: a shifted gather of K into the second buffer, the
+// inverse axis passes and the store pass, which takes the real part (g.y, g.ys, g.ypad).
+hipError_t launch_gen_export(const GenLaunch& g, cf* K, hipStream_t st);
+hipError_t launch_gen_import(const GenLaunch& g, const cf* K, hipStream_t st);
 
 #if defined(__HIPCC__)
 struct DevCtx {

@@ -1153,6 +1153,124 @@ int tb_kspace_mask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs,
 #undef TB_ARGS
 }
 
+// ------------------------------------------------------------ centred spectrum export / import (spectrum.h)
+// Tile of the export / import pass: pass B's width (one tile of LDS, whole 64-B segments per row, 16
+// columns = one 128-B line of 8-byte coefficients per row at H = 240), narrowed until the tile holds
+// at most SP_MAX_TILE coefficients.  Plans that maskgrad_generic() sends to the direct-DFT route go
+// there here as well, so a single column always fits.
+static int spectrum_tile(const tb_plan* p) {
+  int T = pick_tile(p->dev.H, p->lds_max);
+  while (T > 1 && p->dev.H * T > SP_MAX_TILE) --T;
+  return T;
+}
+
+size_t tb_spectrum_workspace_bytes(const tb_plan* plan, int bc) {
+  if (!plan || bc < 0) return 0;
+  const int H = plan->dev.H, W = plan->dev.W, D = plan->dev.D;
+  if (maskgrad_generic(plan)) return gen_workspace_bytes(H, W, D, bc);
+  return (size_t)bc * H * W * (D / 2 + 1) * sizeof(cf);
+}
+
+template <int RA, int RB>
+static int kspace_export(const tb_plan* p, const float* x, const int64_t* xs, cf* K, void* ws, int B, int C,
+                         hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  const bool gen = maskgrad_generic(p);
+  const int T = gen ? 1 : spectrum_tile(p);
+  const int ntiles = (W * Dh + T - 1) / T;
+  const size_t lds = (size_t)tile_geo(H, T).total_cf * sizeof(cf);
+  cf* S = static_cast<cf*>(ws);
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const double vox = (double)nb * C * H * W * D, spec = (double)nb * C * H * W * Dh * 8.0;
+    if (gen) {
+      const GenLaunch g{p->dev, x, xs, nullptr, nullptr, S, 0, b0 * C, C, nb * C, nullptr, nullptr};
+      {
+        Timer t(0, st, vox * 60.0, "k_gen_dft");  // 4 B read and 8 B written by the load, 16 B per axis
+        TB_HIP(tb::launch_gen_spectrum(g, st));
+      }
+      {
+        Timer t(1, st, spec + vox * 8.0, "k_gen_export");
+        TB_HIP(tb::launch_gen_export(g, K, st));
+      }
+      continue;
+    }
+    {
+      Timer t(0, st, vox * 4.0 + spec, use_ct_slab(p) ? "k_slab_fwd_ct16" : "k_slab_fwd");
+      const int rc = launch_slab_fwd<RA>(p, x, xs, S, b0 * C, nb * C, st);
+      if (rc) return rc;
+    }
+    {
+      Timer t(1, st, spec + vox * 8.0, "k_kspace_export");
+      const SpectrumArgs sa{p->dev, S, K, b0 * C, T};
+      TB_HIP(launch_kspace_export<RB>(sa, dim3(ntiles, nb * C), lds, st));
+    }
+  }
+  return TB_OK;
+}
+
+template <int RA, int RB>
+static int kspace_import(const tb_plan* p, const cf* K, float* y, const int64_t* ys, int y_pad, void* ws, int B,
+                         int C, hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  const float scale = (float)(1.0 / ((double)H * (double)W * (double)D));
+  const bool gen = maskgrad_generic(p);
+  const int T = gen ? 1 : spectrum_tile(p);
+  const int ntiles = (W * Dh + T - 1) / T;
+  const size_t lds_b = (size_t)tile_geo(H, T).total_cf * sizeof(cf);
+  const size_t lds_s = (size_t)slab_geo(W, D).total_cf * sizeof(cf);
+  cf* S = static_cast<cf*>(ws);
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const double vox = (double)nb * C * H * W * D, spec = (double)nb * C * H * W * Dh * 8.0;
+    if (gen) {
+      // the gather, three axes and the store pass
+      Timer t(1, st, vox * (8.0 + 16.0 + 3.0 * 16.0) + (double)nb * C * H * W * (D + y_pad) * 4.0, "k_gen_import");
+      const GenLaunch g{p->dev, nullptr, nullptr, y, ys, S, y_pad, b0 * C, C, nb * C, nullptr, nullptr};
+      TB_HIP(tb::launch_gen_import(g, K, st));
+      continue;
+    }
+    {
+      Timer t(1, st, vox * 8.0 + spec, "k_kspace_import");
+      const SpectrumArgs sa{p->dev, S, const_cast<cf*>(K), b0 * C, T};
+      TB_HIP(launch_kspace_import<RB>(sa, dim3(ntiles, nb * C), lds_b, st));
+    }
+    {
+      Timer t(2, st, spec + (double)nb * C * H * W * (D + y_pad) * 4.0, use_ct_slab(p) ? "k_slab_inv_ct" : "k_slab_inv");
+      const SlabInvArgs ia{p->dev, S, y, ys[0], ys[1], ys[2], y_pad, b0 * C, C, scale, nullptr, nb * C};
+      if (use_ct_slab(p))
+        TB_HIP(tb::launch_slab_inv_ct(ia, p->ncu, st));
+      else
+        TB_HIP(launch_slab_inv<RA>(ia, dim3(H, nb * C), lds_s, st));
+    }
+  }
+  return TB_OK;
+}
+
+int tb_kspace_export_f32(const tb_plan* p, const float* x, const int64_t* xs, void* K, void* ws, size_t ws_bytes,
+                         int B, int C, void* stream) {
+  if (!p || !x || !xs || !K || B < 1 || C < 1) return TB_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < tb_spectrum_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define TB_ARGS p, x, xs, static_cast<cf*>(K), ws, B, C, st
+  if (p->rset_wd == RS_SMALL)
+    return p->rset_h == RS_SMALL ? kspace_export<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_export<RS_SMALL, RS_ALL>(TB_ARGS);
+  return p->rset_h == RS_SMALL ? kspace_export<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_export<RS_ALL, RS_ALL>(TB_ARGS);
+#undef TB_ARGS
+}
+
+int tb_kspace_import_f32(const tb_plan* p, const void* K, float* y, const int64_t* ys, int y_pad, void* ws,
+                         size_t ws_bytes, int B, int C, void* stream) {
+  if (!p || !K || !y || !ys || B < 1 || C < 1 || y_pad < 0) return TB_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < tb_spectrum_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define TB_ARGS p, static_cast<const cf*>(K), y, ys, y_pad, ws, B, C, st
+  if (p->rset_wd == RS_SMALL)
+    return p->rset_h == RS_SMALL ? kspace_import<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_import<RS_SMALL, RS_ALL>(TB_ARGS);
+  return p->rset_h == RS_SMALL ? kspace_import<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_import<RS_ALL, RS_ALL>(TB_ARGS);
+#undef TB_ARGS
+}
+
 int tb_kspace_filter_f32(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
                          void* ws, size_t ws_bytes, int B, int C, const tb_sample_ops* ops, uint32_t* minmax,
                          void* stream) {

@@ -31,6 +31,7 @@ from texbias import deferred as _D
 from texbias import kprog as _K
 from texbias import ops as _ops  # registers torch.ops.texbias.*
 from texbias import runtime as _rt
+from texbias import spectrum as _spectrum
 from texbias.shell import shell_coords as _shell_coords
 from texbias.transform_base import (MapTransform, Randomizable, RandomizableTransform, Transform,
                                     ensure_tuple)
@@ -429,15 +430,20 @@ class SegmentationSlicesd(MapTransform, Randomizable):
 class Fourier:
     """Full-spectrum helpers (:594-632).  Not on the filter hot path (the filters never
     materialise a full shifted complex spectrum); provided for API compatibility and run
-    by torch.fft on the tensor's device."""
+    by torch.fft on the tensor's device.  With ``texbias.spectrum.set_dropin(True)`` (default off)
+    CUDA float32 / complex64 tensors take the native passes instead (texbias/spectrum.py)."""
 
     @staticmethod
     def shift_fourier(x: torch.Tensor, n_dims: int) -> torch.Tensor:
+        if _spectrum.takes(x, torch.float32):
+            return _spectrum.shift_fourier(x, n_dims)
         dims = tuple(range(-n_dims, 0))
         return torch.fft.fftshift(torch.fft.fftn(x, dim=dims), dim=dims)
 
     @staticmethod
     def inv_shift_fourier(k: torch.Tensor, n_dims: int) -> torch.Tensor:
+        if _spectrum.takes(k, torch.complex64):
+            return _spectrum.inv_shift_fourier(k, n_dims)
         dims = tuple(range(-n_dims, 0))
         return torch.fft.ifftn(torch.fft.ifftshift(k, dim=dims), dim=dims).real
 

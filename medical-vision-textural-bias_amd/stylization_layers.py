@@ -30,7 +30,7 @@ __all__ = ["Fourier", "GibbsNoiseLayer", "Gibbs_UNet", "spike_layer", "Spikes_UN
 
 
 class Fourier(_Fourier):
-    """Full-spectrum helpers (:16-52), shared with filters_and_operators."""
+    """Full-spectrum helpers (:16-52), shared with filters_and_operators (its drop-in switch included)."""
 
 
 class GibbsNoiseLayer(nn.Module, Fourier):

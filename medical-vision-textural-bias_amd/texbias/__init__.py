@@ -7,6 +7,8 @@ Layering (DESIGN.md):
   transform_base     MONAI-0.5 transform protocol (MONAI's own classes when installed)
   masks              user-supplied k-space masks as transforms (KSpaceMask, KSpaceMaskd) and as a
                      trainable module (LearnedKSpaceMask)
+  spectrum           the centred complex spectrum itself: shift_fourier / inv_shift_fourier on the
+                     native passes, and the default-off drop-in switch of the Fourier helpers
   pipeline           batched device-side augmentation stage (fused chain) for training
   unet / losses      MONAI-equivalent 3-D residual U-Net and DiceLoss (PyTorch-ROCm)
   train              train step, DDP over RCCL
@@ -22,3 +24,11 @@ __version__ = "0.1.0"
 # Set before MIOpen reads them (first convolution); an explicit setting wins.
 for _d in ("FWD", "BWD", "WRW"):
     _os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{_d}", "0")
+
+
+def __getattr__(name):
+    # texbias.spectrum without importing torch at package import
+    if name == "spectrum":
+        import importlib
+        return importlib.import_module(".spectrum", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

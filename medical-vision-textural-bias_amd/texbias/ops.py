@@ -17,6 +17,9 @@ Reference interfaces each op replaces (file:line under the reference root):
                              the reference's only trainable k-space object has d/d alpha = 0 and its
                              drivers update it by finite differences, Gibbs_GD)
   texbias::kspace_mask_grad  the mask gradient on its own
+  texbias::shift_fourier     Fourier.shift_fourier      filters_and_operators.py:594-612 (float32 -> complex64)
+  texbias::inv_shift_fourier Fourier.inv_shift_fourier  filters_and_operators.py:614-632 (complex64 -> float32;
+                             autograd: each is the other's adjoint up to N)
   texbias::gibbs_layer       GibbsNoiseLayer.forward / _apply_mask  stylization_layers.py:79-116
                              (autograd: the filter is self-adjoint; d/d alpha = 0 as in the reference)
 """
@@ -189,6 +192,65 @@ def _kspace_mask_learn_backward(ctx, gy):
 
 
 kspace_mask_learn.register_autograd(_kspace_mask_learn_backward, setup_context=_kspace_mask_learn_setup)
+
+
+@torch.library.custom_op("texbias::shift_fourier", mutates_args=())
+def shift_fourier(x: torch.Tensor, n_dims: int) -> torch.Tensor:
+    """K = fftshift(fftn(x, dims), dims) over the trailing ``n_dims`` axes: float32 in, complex64 out in
+    the centred layout of ``texbias::kspace_mask`` (``runtime.kspace_export``)."""
+    return rt.kspace_export(x, n_dims)
+
+
+@shift_fourier.register_fake
+def _shift_fourier_fake(x, n_dims):
+    return x.new_empty(x.shape, dtype=torch.complex64)
+
+
+@torch.library.custom_op("texbias::inv_shift_fourier", mutates_args=())
+def inv_shift_fourier(k: torch.Tensor, n_dims: int, pad: int = 0) -> torch.Tensor:
+    """y = Re(ifftn(ifftshift(k, dims), dims)) over the trailing ``n_dims`` axes for any complex64 ``k``
+    (last axis padded by ``pad`` zero columns): float32 out (``runtime.kspace_import``)."""
+    return rt.kspace_import(k, n_dims, pad=pad)
+
+
+@inv_shift_fourier.register_fake
+def _inv_shift_fourier_fake(k, n_dims, pad=0):
+    return k.new_empty(tuple(k.shape[:-1]) + (k.shape[-1] + pad,), dtype=torch.float32)
+
+
+def _spatial_count(shape, n_dims: int) -> float:
+    return float(int(np.prod([int(s) for s in shape[len(shape) - n_dims:]])))
+
+
+# The two maps are each other's adjoint up to N = the number of transformed voxels: with the upstream
+# gradient of a complex tensor in PyTorch's convention dL/dRe + i dL/dIm,
+#   K = shift_fourier(x):      gx = N inv_shift_fourier(gK)
+#   y = inv_shift_fourier(K):  gK = shift_fourier(gy[..., :D]) / N   (the zero pad columns take no gradient)
+# Each backward is the other op, so both are differentiable any number of times.
+def _shift_fourier_setup(ctx, inputs, output):
+    x, n_dims = inputs
+    ctx.n_dims, ctx.n = n_dims, _spatial_count(x.shape, n_dims)
+
+
+def _shift_fourier_backward(ctx, gk):
+    if not ctx.needs_input_grad[0]:
+        return None, None
+    return torch.ops.texbias.inv_shift_fourier(gk, ctx.n_dims, 0) * ctx.n, None
+
+
+def _inv_shift_fourier_setup(ctx, inputs, output):
+    k, n_dims, pad = inputs
+    ctx.n_dims, ctx.d, ctx.n = n_dims, k.shape[-1], _spatial_count(k.shape, n_dims)
+
+
+def _inv_shift_fourier_backward(ctx, gy):
+    if not ctx.needs_input_grad[0]:
+        return None, None, None
+    return torch.ops.texbias.shift_fourier(gy[..., : ctx.d], ctx.n_dims) / ctx.n, None, None
+
+
+shift_fourier.register_autograd(_shift_fourier_backward, setup_context=_shift_fourier_setup)
+inv_shift_fourier.register_autograd(_inv_shift_fourier_backward, setup_context=_inv_shift_fourier_setup)
 
 
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

@@ -358,6 +358,95 @@ def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channel
     return dm
 
 
+def _spectrum_args(what: str, t: torch.Tensor, n_dims: int, dtype: torch.dtype) -> Tuple[Geometry, int]:
+    """Host-side check of an export / import argument [*lead, *spatial]: (geometry, volumes)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a torch tensor is expected, got {type(t).__name__}")
+    n_dims = int(n_dims)
+    if n_dims < 1 or t.dim() < n_dims:
+        raise ValueError(f"{what}: {n_dims} transformed axes on a {t.dim()}-d tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: {dtype} expected, got {t.dtype}")
+    lead = t.shape[: t.dim() - n_dims]
+    if t.device.type != "cuda":
+        raise TexbiasError(f"{what}: expected a HIP (cuda) tensor, got {t.device}")
+    return geometry(tuple(t.shape[t.dim() - n_dims:])), (int(np.prod(lead)) if len(lead) else 1)
+
+
+def _image_strides(t: torch.Tensor, n_dims: int, geo: Geometry):
+    """(bc stride, h stride, w stride) of an image, or None when it is not addressable in place (leading
+    axes that do not collapse, a strided last axis)."""
+    v = _bc_view(t, n_dims)
+    if v is None:
+        return None
+    sh, sw, sd = _hwd_strides(geo, v[3])
+    if sd != 1:
+        return None
+    return (C.c_int64 * 3)(v[1], sh, sw)
+
+
+def kspace_export(x: torch.Tensor, n_dims: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K = fftshift(fftn(x, dims), dims) over the trailing ``n_dims`` axes (``Fourier.shift_fourier``):
+    ``x`` float32 [*lead, *spatial] with any strides and a contiguous last axis (read in place), K complex64
+    of x's shape, contiguous, in the centred layout of ``kspace_mask``.  Pass A and one per-coefficient
+    pass on the current stream (``tb_kspace_export_f32``); every element of K is written once, f and -f
+    from one value, so repeated calls agree bit for bit.  ``out``: a complex64 contiguous tensor of x's
+    shape on its device to overwrite (it need not be zeroed)."""
+    geo, bc = _spectrum_args("kspace_export", x, n_dims, torch.float32)
+    H, W, D = geo.hwd
+    xs = _image_strides(x, n_dims, geo)
+    if xs is None:
+        x = x.contiguous()
+        xs = _image_strides(x, n_dims, geo)
+    if out is None:
+        k = torch.empty(x.shape, dtype=torch.complex64, device=x.device)
+    else:
+        k = out
+        if (not isinstance(k, torch.Tensor) or tuple(k.shape) != tuple(x.shape) or k.dtype != torch.complex64
+                or not k.is_contiguous() or k.device != x.device):
+            raise ValueError(f"kspace_export: out must be a complex64 contiguous {tuple(x.shape)} tensor on {x.device}")
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_spectrum_workspace_bytes(plan.handle, bc)))
+        check(lib().tb_kspace_export_f32(plan.handle, x.data_ptr(), xs, k.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         bc, 1, _stream(x.device)), "tb_kspace_export_f32")
+    return k
+
+
+def kspace_import(k: torch.Tensor, n_dims: int, pad: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = Re(ifftn(ifftshift(k, dims), dims)) over the trailing ``n_dims`` axes
+    (``Fourier.inv_shift_fourier``) for any complex64 ``k`` [*lead, *spatial] -- it need not be Hermitian:
+    the result is the exact inverse of the symmetrised (k(f) + conj(k(-f))) / 2.  ``pad`` appends zero
+    columns to the last axis.  One per-coefficient pass and pass C on the current stream
+    (``tb_kspace_import_f32``).  ``out``: a float32 tensor [*lead, *spatial[:-1], D + pad] on k's device
+    with a contiguous last axis; a strided view is written in place, bytes outside it are not touched."""
+    geo, bc = _spectrum_args("kspace_import", k, n_dims, torch.complex64)
+    H, W, D = geo.hwd
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError(f"kspace_import: pad must be >= 0, got {pad}")
+    if pad and len(geo.kept) and geo.kept[-1] != n_dims - 1:
+        raise ValueError("kspace_import: padding requires a non-singleton last axis")
+    k = k.resolve_conj().contiguous()   # a lazily conjugated view shares its base's memory
+    shape = tuple(k.shape[:-1]) + (k.shape[-1] + pad,)
+    if out is None:
+        y = torch.empty(shape, dtype=torch.float32, device=k.device)
+    else:
+        y = out
+        if (not isinstance(y, torch.Tensor) or tuple(y.shape) != shape or y.dtype != torch.float32
+                or y.device != k.device):
+            raise ValueError(f"kspace_import: out must be a float32 {shape} tensor on {k.device}")
+    ys = _image_strides(y, n_dims, geo)
+    if ys is None:
+        raise ValueError("kspace_import: out must collapse its leading axes and have a contiguous last axis")
+    plan = plan_for(k.device, H, W, D)
+    with torch.cuda.device(k.device):
+        ws = workspace(k.device, int(lib().tb_spectrum_workspace_bytes(plan.handle, bc)))
+        check(lib().tb_kspace_import_f32(plan.handle, k.data_ptr(), y.data_ptr(), ys, pad, ws.data_ptr(), ws.numel(),
+                                         bc, 1, _stream(k.device)), "tb_kspace_import_f32")
+    return y
+
+
 def minmax_buffer(device: torch.device, B: int) -> torch.Tensor:
     idx = device.index if device.index is not None else torch.cuda.current_device()
     m = _mm.get(idx)

@@ -26,21 +26,27 @@ import torch.nn as nn
 
 from filters_and_operators import _kspace
 from texbias import kprog as _K
+from texbias import spectrum as _spectrum
 from texbias.transform_base import Transform
 
 __all__ = ["FourierTransform", "RandZF", "freq_consistency_loss", "FreqConsistencyLoss", "weights_init"]
 
 
 class FourierTransform:
-    """Centred FFT helpers over the trailing ``n_dims`` axes (utils2.py:6-31)."""
+    """Centred FFT helpers over the trailing ``n_dims`` axes (utils2.py:6-31); the native passes with
+    ``texbias.spectrum.set_dropin(True)`` (default off)."""
 
     @staticmethod
     def shift_fourier(x: torch.Tensor, n_dims: int) -> torch.Tensor:
+        if _spectrum.takes(x, torch.float32):
+            return _spectrum.shift_fourier(x, n_dims)
         dims = tuple(range(-n_dims, 0))
         return torch.fft.fftshift(torch.fft.fftn(x, dim=dims), dim=dims)
 
     @staticmethod
     def inv_shift_fourier(k: torch.Tensor, n_dims: int) -> torch.Tensor:
+        if _spectrum.takes(k, torch.complex64):
+            return _spectrum.inv_shift_fourier(k, n_dims)
         dims = tuple(range(-n_dims, 0))
         return torch.fft.ifftn(torch.fft.ifftshift(k, dim=dims), dim=dims).real
 
