@@ -70,6 +70,16 @@ extern "C" {
                          taken): the caller keeps it alive until the launch has run on `stream`; values
                          written to it in stream order before the launch, or between replays of a captured
                          graph, apply.  The gradient of y with respect to M: tb_kspace_mask_grad_f32 below */
+#define TB_OP_CMASK 8 /* the caller's own COMPLEX k-space mask: as TB_OP_MASK with l = DEVICE address of a
+                         contiguous complex64 M[Cm][H][W][D] (interleaved re, im) in the same centred layout;
+                         i[0] = Cm, i[1] = W, i[2] = D and the argument checks are those of TB_OP_MASK.
+                         y = Re(IFFT(ifftshift(M . fftshift(FFT x)))): on the Hermitian spectrum the .real
+                         leaves each stored coefficient multiplied by the complex factor
+                         c(f) = (M[s(f)] + conj(M[s(-f)])) / 2, which is Re M at a self-conjugate f (a phase
+                         ramp, a B0-like phase, a complex apodisation).  reserved = 1: multiply by conj(c)
+                         instead -- the adjoint Re(IFFT(ifftshift(conj(M) . fftshift(FFT g)))) of the same
+                         op, with no conj(M) materialised.  Lifetime and stream order as for TB_OP_MASK.
+                         The gradient of y with respect to M: tb_kspace_cmask_grad_f32 below */
 
 #define TB_MAX_OPS 6
 #define TB_MAX_BATCH 8 /* samples per launch group; larger batches are split by the library */
@@ -187,6 +197,20 @@ int tb_kspace_logabs_sum_f32(const tb_plan* plan, const float* x, const int64_t*
 size_t tb_mask_grad_workspace_bytes(const tb_plan* plan, int bc);
 int tb_kspace_mask_grad_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
                             float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream);
+
+/*
+ * Gradient of the TB_OP_CMASK round trip with respect to the complex mask M, in torch.autograd's convention for
+ * a complex leaf:
+ *   dM[s(f)] = sum conj(X(f)) G(f) / (H W D),   X = FFT(x), G = FFT(g)
+ * so dM[s(-f)] = conj(dM[s(f)]), dM is real at a self-conjugate f, and its real part is what
+ * tb_kspace_mask_grad_f32 gives.  dM: device, contiguous complex64 [Cm][H][W][D] (interleaved re, im), centred
+ * layout; overwritten completely, every element written exactly once.  Every other argument, the workspace
+ * (tb_mask_grad_workspace_bytes), the sums over samples and channels and the error codes are those of
+ * tb_kspace_mask_grad_f32.  The gradient with respect to x is the op itself with reserved = 1.
+ */
+int tb_kspace_cmask_grad_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                             void* dM /* complex64 [Cm][H][W][D] */, int Cm, void* ws, size_t ws_bytes, int B, int C,
+                             void* stream);
 
 /*
  * The centred complex spectrum itself (Fourier.shift_fourier / inv_shift_fourier,

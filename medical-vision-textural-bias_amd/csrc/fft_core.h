@@ -649,6 +649,14 @@ TB_HD int64_t mask_index(int64_t ch, int kh, int kw, int kd, int H, int W, int D
 }
 // y = Re(IFFT(ifftshift(M . fftshift(FFT x)))): the .real symmetrises, exact for a real M
 TB_HD float mask_factor(float mf, float mn) { return 0.5f * (mf + mn); }
+// TB_OP_CMASK: the same round trip with a complex M (interleaved re, im; indexed by mask_index).  On the
+// Hermitian spectrum the .real leaves the complex factor (M[s(f)] + conj(M[s(-f)])) / 2 per stored
+// coefficient, Re M at a self-conjugate f; `cj` gives its conjugate, the adjoint's factor (conj(M) is
+// never materialised).
+TB_HD cf cmask_factor(cf mf, cf mn, bool cj) {
+  const float im = 0.5f * (mf.y - mn.y);
+  return mk(0.5f * (mf.x + mn.x), cj ? -im : im);
+}
 
 // Apply a sample's op program to one stored half-spectrum coefficient.
 // Every op is followed by the reference's `.real` (G4: Hermitian symmetrisation);
@@ -716,6 +724,13 @@ TB_HD cf apply_ops(const SO& so, int chan, cf v, const FreqCol& fc, int kh, int 
         const int64_t ch = op.i[0] > 1 ? (int64_t)chan * H : 0;
         v = scl(v, mask_factor(M[mask_index(ch, kh, fc.kw, fc.kd, H, Wm, Dm)],
                                M[mask_index(ch, h.nk, fc.nkw, fc.nkd, H, Wm, Dm)]));
+      } break;
+      case TB_OP_CMASK: {  // the caller's complex mask: one 8-byte load at f and one at -f
+        const cf* M = reinterpret_cast<const cf*>(op.l);
+        const int Wm = op.i[1], Dm = op.i[2];
+        const int64_t ch = op.i[0] > 1 ? (int64_t)chan * H : 0;
+        v = mul(v, cmask_factor(M[mask_index(ch, kh, fc.kw, fc.kd, H, Wm, Dm)],
+                                M[mask_index(ch, h.nk, fc.nkw, fc.nkd, H, Wm, Dm)], op.reserved == 1));
       } break;
       default: break;
     }

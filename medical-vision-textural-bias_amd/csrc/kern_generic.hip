@@ -177,6 +177,7 @@ struct GenMaskGradArgs {
   float* dM;
   int H, W, D, C, nb, Cm, accumulate;
   float scale;
+  int cplx;  // dM complex64: conj(X) G / N at f, its conjugate at -f (the TB_OP_CMASK gradient)
 };
 __global__ __launch_bounds__(NT_GEN) void k_gen_maskgrad(GenMaskGradArgs a) {
   const int H = a.H, W = a.W, D = a.D, Dh = D / 2 + 1;
@@ -188,13 +189,24 @@ __global__ __launch_bounds__(NT_GEN) void k_gen_maskgrad(GenMaskGradArgs a) {
     const int64_t hw = e / Dh;
     const int kd = (int)(e - hw * Dh), kh = (int)(hw / W), kw = (int)(hw - (int64_t)kh * W);
     const int64_t src = hw * D + kd;
-    float acc = 0.f;
+    float acc = 0.f, acc2 = 0.f;
     for (int k = 0; k < nv; ++k) {
       const int64_t vol = a.Cm == 1 ? k : (int64_t)k * a.C + slot;
       const cf x = a.S[vol * n + src], g = a.Sg[vol * n + src];
       acc += x.x * g.x + x.y * g.y;
+      acc2 += x.x * g.y - x.y * g.x;
     }
     const float v = acc * a.scale;
+    if (a.cplx) {
+      const float w = acc2 * a.scale;
+      cf* p = reinterpret_cast<cf*>(a.dM) + mask_index((int64_t)slot * H, kh, kw, kd, H, W, D);
+      *p = a.accumulate ? mk(p->x + v, p->y + w) : mk(v, w);
+      if (kd != 0 && kd != Dtop) {
+        cf* q = reinterpret_cast<cf*>(a.dM) + mask_index((int64_t)slot * H, negk(kh, H), negk(kw, W), D - kd, H, W, D);
+        *q = a.accumulate ? mk(q->x + v, q->y - w) : mk(v, -w);
+      }
+      continue;
+    }
     float* p = a.dM + mask_index((int64_t)slot * H, kh, kw, kd, H, W, D);
     *p = a.accumulate ? *p + v : v;
     if (kd != 0 && kd != Dtop) {
@@ -349,10 +361,10 @@ hipError_t launch_gen_spectrum(const GenLaunch& g, hipStream_t st) {
 }
 
 hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, float* dM, int C, int nb, int Cm,
-                               int accumulate, hipStream_t st) {
+                               int accumulate, hipStream_t st, int cplx) {
   const int64_t n = (int64_t)pl.H * pl.W * pl.D;
   const GenMaskGradArgs m{X, G, dM, pl.H, pl.W, pl.D, C, nb, Cm, accumulate,
-                          (float)(1.0 / ((double)pl.H * (double)pl.W * (double)pl.D))};
+                          (float)(1.0 / ((double)pl.H * (double)pl.W * (double)pl.D)), cplx};
   hipLaunchKernelGGL(k_gen_maskgrad, dim3(gen_blocks(n / 2 + 1), Cm), dim3(NT_GEN), 0, st, m);
   return hipGetLastError();
 }

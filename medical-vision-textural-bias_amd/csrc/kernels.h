@@ -69,7 +69,8 @@ template <int RS> hipError_t launch_slab_fwd(const SlabFwdArgs& a, dim3 grid, si
 template <int RS> hipError_t launch_kspace(const KspaceArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_slab_inv(const SlabInvArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_kspace_stats(const StatsArgs& a, dim3 grid, size_t lds, hipStream_t st);
-// mask gradient (maskgrad.h, kern_maskgrad.hip): grid = (tiles of a.T columns, mask channel slots)
+// mask gradient (maskgrad.h, kern_maskgrad.hip): grid = (tiles of a.T columns, mask channel slots);
+// a.cplx picks k_kspace_cmaskgrad
 template <int RS> hipError_t launch_kspace_maskgrad(const MaskGradArgs& a, dim3 grid, size_t lds, hipStream_t st);
 // centred spectrum export / import (spectrum.h, kern_spectrum.hip): grid = (tiles of a.T columns, volumes)
 template <int RS> hipError_t launch_kspace_export(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
@@ -115,8 +116,9 @@ hipError_t launch_gen_logabs(const GenLaunch& g, double* out, hipStream_t st);
 // element-wise k_gen_maskgrad over the full spectra of the group's nb samples.
 size_t gen_maskgrad_workspace_bytes(int H, int W, int D, int bc);
 hipError_t launch_gen_spectrum(const GenLaunch& g, hipStream_t st);
+// cplx: dM is complex64 and takes conj(X) G / N (the TB_OP_CMASK gradient).
 hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, float* dM, int C, int nb, int Cm,
-                               int accumulate, hipStream_t st);
+                               int accumulate, hipStream_t st, int cplx = 0);
 // Centred spectrum on the fallback, in the two buffers of gen_workspace_bytes.  launch_gen_export: after
 // launch_gen_spectrum(g), a shifted copy of the spectrum's kd <= D/2 half into K[bc][H][W][D] with the
 // write-once rule of spectrum.h.  launch_gen_import: a shifted gather of K into the second buffer, the

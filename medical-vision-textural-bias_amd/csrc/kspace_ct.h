@@ -125,6 +125,24 @@ TB_HD void ops_bfly(const SO& so, int chan, v2* v, const FreqCol& fc, int kh0, i
         TB_UNROLL
         for (int q = 0; q < R; ++q) v[q] = mask_factor(mf[q], mn[q]) * v[q];
       } break;
+      case TB_OP_CMASK: {  // as MASK with 8-byte complex values: all 2 R loads ahead of the first use
+        const cf* M = reinterpret_cast<const cf*>(op.l);
+        const int Wm = op.i[1], Dm = op.i[2];
+        const int64_t ch = op.i[0] > 1 ? (int64_t)chan * H : 0;
+        const bool cj = op.reserved == 1;
+        cf mf[R], mn[R];
+        TB_UNROLL
+        for (int q = 0; q < R; ++q) {
+          const int kh = kh0 + kst * q;
+          mf[q] = M[mask_index(ch, kh, fc.kw, fc.kd, H, Wm, Dm)];
+          mn[q] = M[mask_index(ch, negk(kh, H), fc.nkw, fc.nkd, H, Wm, Dm)];
+        }
+        TB_UNROLL
+        for (int q = 0; q < R; ++q) {
+          const cf c = cmask_factor(mf[q], mn[q], cj);
+          v[q] = cmul(v[q], V(c.x, c.y));
+        }
+      } break;
       default: break;
     }
   }

@@ -14,6 +14,12 @@
 // centred position of f = (irev_h[h'], irev_w[w'], kd) and, when kd is not self-conjugate, of -f.  In a
 // self-conjugate column (kd = 0, kd = D/2 with D even) -f is itself a stored coefficient and is
 // written by its owner, so every element of dM is written exactly once and no atomics are needed.
+//
+// The complex mask of TB_OP_CMASK (CX = true, MaskGradArgs::cplx) has the complex gradient
+//     dL/dM[s(f)] = conj(X(f)) G(f) / N      (the convention of torch.autograd for a complex leaf),
+// whose real part is the value above.  The unit keeps a second accumulator x.re g.im - x.im g.re per
+// coefficient, stores a cf at f and its conjugate at -f (dM is then complex64 [Cm][H][W][D]); tiles,
+// ownership of the self-conjugate columns and `accumulate` are unchanged.
 #pragma once
 
 #include "fft_core.h"
@@ -29,6 +35,7 @@ struct MaskGradArgs {
   int T;               // tile width in columns; H * T <= MG_MAX_TILE
   int accumulate;      // 0: dM = v;  1: dM += v (launch groups after the first)
   float scale;         // 1 / N
+  int cplx;            // 1: dM is complex64 (interleaved re, im), the gradient of a TB_OP_CMASK mask
 };
 
 constexpr int MG_NE = 8;            // coefficients per thread of k_kspace_maskgrad
@@ -79,10 +86,10 @@ TB_HD void mg_to_lds(const MgTile& g, int ne, cf* lds, const cf* r) {
 TB_HD int mg_volume(const MaskGradArgs& a, int slot, int k) { return a.Cm == 1 ? a.bc0 + k : a.bc0 + k * a.C + slot; }
 
 // xa, ga: NE (or ne) complex slots per thread; acc: as many floats.  PF: load the next volume's tiles
-// before the transform of the current one.
-template <class Ctx, int RS, int NE, bool PF>
+// before the transform of the current one.  CX: the complex gradient, with acc2 as many floats again.
+template <class Ctx, int RS, int NE, bool PF, bool CX = false>
 TB_HD void maskgrad_unit(Ctx& ctx, cf* lds, const MaskGradArgs& a, int slot, int tile, int ne, cf* xa, cf* ga,
-                         float* acc) {
+                         float* acc, float* acc2 = nullptr) {
   const tb_plan_dev& pl = a.pl;
   const int H = pl.H, W = pl.W, D = pl.D, Dh = D / 2 + 1, T = a.T;
   const int ncols_all = W * Dh;
@@ -96,6 +103,7 @@ TB_HD void maskgrad_unit(Ctx& ctx, cf* lds, const MaskGradArgs& a, int slot, int
   const int64_t vstride = (int64_t)H * ncols_all;
   const int nv = a.Cm == 1 ? a.nb * a.C : a.nb;
   TB_MG_EACH(i) acc[i] = 0.f;
+  if (CX) { TB_MG_EACH(i) acc2[i] = 0.f; }
   if (PF) {
     const int64_t v0 = mg_volume(a, slot, 0);
     mg_load<NE>(g, ne, a.Sx + v0 * vstride + j0, xa);
@@ -121,6 +129,7 @@ TB_HD void maskgrad_unit(Ctx& ctx, cf* lds, const MaskGradArgs& a, int slot, int
       if (g.at(i, hh, c)) {
         const cf x = lds[g.slot(hh, c)], v = lds[g.slot(hh, c) + nc];
         acc[i] += x.x * v.x + x.y * v.y;
+        if (CX) acc2[i] += x.x * v.y - x.y * v.x;
       }
     }
     ctx.sync();
@@ -135,6 +144,16 @@ TB_HD void maskgrad_unit(Ctx& ctx, cf* lds, const MaskGradArgs& a, int slot, int
     const int wp = j / Dh, kd = j - wp * Dh;
     const int kh = irev[hp], kw = pl.irev_w[wp];
     const float v = acc[i] * a.scale;
+    if (CX) {
+      const float w = acc2[i] * a.scale;
+      cf* p = reinterpret_cast<cf*>(a.dM) + mask_index(ch, kh, kw, kd, H, W, D);
+      *p = a.accumulate ? mk(p->x + v, p->y + w) : mk(v, w);
+      if (kd != 0 && kd != Dtop) {
+        cf* q = reinterpret_cast<cf*>(a.dM) + mask_index(ch, negk(kh, H), negk(kw, W), D - kd, H, W, D);
+        *q = a.accumulate ? mk(q->x + v, q->y - w) : mk(v, -w);
+      }
+      continue;
+    }
     float* p = a.dM + mask_index(ch, kh, kw, kd, H, W, D);
     *p = a.accumulate ? *p + v : v;
     if (kd != 0 && kd != Dtop) {

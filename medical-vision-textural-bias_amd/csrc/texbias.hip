@@ -941,12 +941,12 @@ static int run_copy(const tb_plan* p, const float* x, const int64_t* xs, float* 
   return TB_OK;
 }
 
-// TB_OP_MASK ops carry a device address the kernels dereference: checked here, before any launch
+// TB_OP_MASK / TB_OP_CMASK ops carry a device address the kernels dereference: checked here, before any launch
 static bool mask_ops_ok(const tb_plan* p, const tb_sample_ops* ops, int B, int C) {
   for (int b = 0; b < B; ++b)
     for (int o = 0; o < ops[b].n && o < TB_MAX_OPS; ++o) {
       const tb_op& op = ops[b].op[o];
-      if (op.kind != TB_OP_MASK) continue;
+      if (op.kind != TB_OP_MASK && op.kind != TB_OP_CMASK) continue;
       if (op.l == 0 || op.i[1] != p->dev.W || op.i[2] != p->dev.D || (op.i[0] != 1 && op.i[0] != C)) return false;
     }
   return true;
@@ -1092,9 +1092,10 @@ size_t tb_mask_grad_workspace_bytes(const tb_plan* plan, int bc) {
 
 template <int RA, int RB>
 static int kspace_mask_grad(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
-                            float* dM, int Cm, void* ws, int B, int C, hipStream_t st) {
+                            float* dM, int Cm, void* ws, int B, int C, hipStream_t st, int cplx) {
   const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
   const double scale = 1.0 / ((double)H * (double)W * (double)D);
+  const double dm_bytes = (double)Cm * H * W * D * (cplx ? 8.0 : 4.0);
   if (maskgrad_generic(p)) {
     for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
       const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
@@ -1111,8 +1112,8 @@ static int kspace_mask_grad(const tb_plan* p, const float* x, const int64_t* xs,
         TB_HIP(tb::launch_gen_spectrum(gg, st));
       }
       {
-        Timer t(1, st, 2.0 * (double)nb * C * H * W * Dh * 8.0 + (double)Cm * H * W * D * 4.0, "k_gen_maskgrad");
-        TB_HIP(tb::launch_gen_maskgrad(p->dev, b2p, b1p, dM, C, nb, Cm, b0 > 0 ? 1 : 0, st));
+        Timer t(1, st, 2.0 * (double)nb * C * H * W * Dh * 8.0 + dm_bytes, "k_gen_maskgrad");
+        TB_HIP(tb::launch_gen_maskgrad(p->dev, b2p, b1p, dM, C, nb, Cm, b0 > 0 ? 1 : 0, st, cplx));
       }
     }
     return TB_OK;
@@ -1133,24 +1134,34 @@ static int kspace_mask_grad(const tb_plan* p, const float* x, const int64_t* xs,
       if (rc) return rc;
     }
     {
-      Timer t(1, st, 2.0 * spec + (double)Cm * H * W * D * 4.0, "k_kspace_maskgrad");
-      const MaskGradArgs ma{p->dev, Sx, Sg, dM, b0 * C, C, nb, Cm, T, b0 > 0 ? 1 : 0, (float)scale};
+      Timer t(1, st, 2.0 * spec + dm_bytes, cplx ? "k_kspace_cmaskgrad" : "k_kspace_maskgrad");
+      const MaskGradArgs ma{p->dev, Sx, Sg, dM, b0 * C, C, nb, Cm, T, b0 > 0 ? 1 : 0, (float)scale, cplx};
       TB_HIP(launch_kspace_maskgrad<RB>(ma, dim3(ntiles, Cm), lds, st));
     }
   }
   return TB_OK;
 }
 
-int tb_kspace_mask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
-                            float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+static int mask_grad_entry(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                           float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream, int cplx) {
   if (!p || !x || !xs || !g || !gs || !dM || B < 1 || C < 1 || (Cm != 1 && Cm != C)) return TB_ERR_INVALID_ARG;
   if (!ws || ws_bytes < tb_mask_grad_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define TB_ARGS p, x, xs, g, gs, dM, Cm, ws, B, C, st
+#define TB_ARGS p, x, xs, g, gs, dM, Cm, ws, B, C, st, cplx
   if (p->rset_wd == RS_SMALL)
     return p->rset_h == RS_SMALL ? kspace_mask_grad<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_mask_grad<RS_SMALL, RS_ALL>(TB_ARGS);
   return p->rset_h == RS_SMALL ? kspace_mask_grad<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_mask_grad<RS_ALL, RS_ALL>(TB_ARGS);
 #undef TB_ARGS
+}
+
+int tb_kspace_mask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                            float* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+  return mask_grad_entry(p, x, xs, g, gs, dM, Cm, ws, ws_bytes, B, C, stream, 0);
+}
+
+int tb_kspace_cmask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                             void* dM, int Cm, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+  return mask_grad_entry(p, x, xs, g, gs, static_cast<float*>(dM), Cm, ws, ws_bytes, B, C, stream, 1);
 }
 
 // ------------------------------------------------------------ centred spectrum export / import (spectrum.h)

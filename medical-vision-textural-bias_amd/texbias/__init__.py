@@ -6,7 +6,7 @@ Layering (DESIGN.md):
   shell              plane-wave ellipsoid shell candidates
   transform_base     MONAI-0.5 transform protocol (MONAI's own classes when installed)
   masks              user-supplied k-space masks as transforms (KSpaceMask, KSpaceMaskd) and as a
-                     trainable module (LearnedKSpaceMask)
+                     trainable module (LearnedKSpaceMask); their complex64 forms (ComplexKSpaceMask, ...)
   spectrum           the centred complex spectrum itself: shift_fourier / inv_shift_fourier on the
                      native passes, and the default-off drop-in switch of the Fourier helpers
   pipeline           batched device-side augmentation stage (fused chain) for training

@@ -21,6 +21,7 @@ TB_OP_WRAP = 4
 TB_OP_ZF = 6
 TB_OP_SPIKE = 5
 TB_OP_MASK = 7
+TB_OP_CMASK = 8
 
 TB_MAX_OPS = 6
 TB_MAX_BATCH = 8

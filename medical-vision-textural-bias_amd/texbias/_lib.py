@@ -42,6 +42,7 @@ def _proto(L):
         "tb_kspace_logabs_sum_f32": (I, [P, P, P, P, SZ, I, I, P, P, P]),
         "tb_mask_grad_workspace_bytes": (SZ, [P, I]),
         "tb_kspace_mask_grad_f32": (I, [P, P, P, P, P, P, I, P, SZ, I, I, P]),
+        "tb_kspace_cmask_grad_f32": (I, [P, P, P, P, P, P, I, P, SZ, I, I, P]),
         "tb_spectrum_workspace_bytes": (SZ, [P, I]),
         "tb_kspace_export_f32": (I, [P, P, P, P, P, SZ, I, I, P]),
         "tb_kspace_import_f32": (I, [P, P, P, P, I, P, SZ, I, I, P]),

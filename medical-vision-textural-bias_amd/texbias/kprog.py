@@ -22,8 +22,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import (TB_MAX_OPS, TB_OP_DISK, TB_OP_GIBBS, TB_OP_LAYER, TB_OP_MASK, TB_OP_SPIKE, TB_OP_WRAP, TB_OP_ZF,
-                   TbOp)
+from ._abi import (TB_MAX_OPS, TB_OP_CMASK, TB_OP_DISK, TB_OP_GIBBS, TB_OP_LAYER, TB_OP_MASK, TB_OP_SPIKE, TB_OP_WRAP,
+                   TB_OP_ZF, TbOp)
 
 
 @dataclass(frozen=True)
@@ -193,6 +193,22 @@ def mask_op(mask_ptr: int, mask_channels: int, hwd: Sequence[int], chan: int = -
     op.l = int(mask_ptr)
     op.i[0] = int(mask_channels)
     op.i[1], op.i[2] = int(hwd[1]), int(hwd[2])
+    return op
+
+
+def cmask_op(mask_ptr: int, mask_channels: int, hwd: Sequence[int], chan: int = -1, conj: bool = False) -> TbOp:
+    """The caller's own complex k-space mask (TB_OP_CMASK in include/texbias.h): as ``mask_op`` with
+    ``mask_ptr`` the device address of a contiguous complex64 ``M[mask_channels][H][W][D]`` (interleaved
+    re, im).  ``conj``: apply conj(M) instead -- the adjoint of the same op, read from the same buffer."""
+    if not mask_ptr:
+        raise ValueError("cmask_op needs the device address of the mask")
+    if int(mask_channels) < 1:
+        raise ValueError(f"mask_channels must be 1 or the channel count, got {mask_channels}")
+    op = _op(TB_OP_CMASK, chan)
+    op.l = int(mask_ptr)
+    op.i[0] = int(mask_channels)
+    op.i[1], op.i[2] = int(hwd[1]), int(hwd[2])
+    op.reserved = 1 if conj else 0
     return op
 
 

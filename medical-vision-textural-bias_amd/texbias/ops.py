@@ -17,6 +17,8 @@ Reference interfaces each op replaces (file:line under the reference root):
                              the reference's only trainable k-space object has d/d alpha = 0 and its
                              drivers update it by finite differences, Gibbs_GD)
   texbias::kspace_mask_grad  the mask gradient on its own
+  texbias::kspace_cmask, kspace_cmask_learn, kspace_cmask_grad   the same three for a complex64 mask (a phase
+                             ramp or any complex factor multiplied into Fourier.shift_fourier(x)  :594-632)
   texbias::shift_fourier     Fourier.shift_fourier      filters_and_operators.py:594-612 (float32 -> complex64)
   texbias::inv_shift_fourier Fourier.inv_shift_fourier  filters_and_operators.py:614-632 (complex64 -> float32;
                              autograd: each is the other's adjoint up to N)
@@ -192,6 +194,89 @@ def _kspace_mask_learn_backward(ctx, gy):
 
 
 kspace_mask_learn.register_autograd(_kspace_mask_learn_backward, setup_context=_kspace_mask_learn_setup)
+
+
+@torch.library.custom_op("texbias::kspace_cmask", mutates_args=())
+def kspace_cmask(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: int, pad: int = 0,
+                 conj: bool = False) -> torch.Tensor:
+    """``texbias::kspace_mask`` with a complex64 mask (TB_OP_CMASK): y = Re(IFFT(ifftshift(mask *
+    fftshift(FFT(x))))), ``spatial`` or ``(channels,) + spatial``, contiguous, on x's device.  ``conj``:
+    conj(mask) instead, the adjoint of the same op, read from the same buffer."""
+    return rt.kspace_cmask(x, mask, n_dims, pad=pad, channels=channels, conj=conj)
+
+
+@kspace_cmask.register_fake
+def _kspace_cmask_fake(x, mask, n_dims, channels, pad=0, conj=False):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+
+
+def _kspace_cmask_setup(ctx, inputs, output):
+    x, mask, n_dims, channels, pad, conj = inputs
+    if mask.requires_grad:
+        raise ValueError("texbias::kspace_cmask has no gradient w.r.t. the mask (use texbias::kspace_cmask_learn)")
+    ctx.save_for_backward(mask)
+    ctx.n_dims, ctx.channels, ctx.d, ctx.conj = n_dims, channels, x.shape[-1], conj
+
+
+def _kspace_cmask_backward(ctx, gy):
+    # the adjoint of x -> Re(IFFT(M FFT x)) is g -> Re(IFFT(conj(M) FFT g)): the same op with the
+    # conjugate flag toggled; the zero pad columns take no gradient
+    (mask,) = ctx.saved_tensors
+    gx = torch.ops.texbias.kspace_cmask(gy[..., : ctx.d], mask, ctx.n_dims, ctx.channels, 0, not ctx.conj)
+    return gx, None, None, None, None, None
+
+
+kspace_cmask.register_autograd(_kspace_cmask_backward, setup_context=_kspace_cmask_setup)
+
+
+@torch.library.custom_op("texbias::kspace_cmask_grad", mutates_args=())
+def kspace_cmask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, channels: int, mask_channels: int) -> torch.Tensor:
+    """Gradient of ``kspace_cmask(x, M)`` with respect to the complex mask for the upstream gradient ``g``:
+    complex64, conj(FFT x) FFT g / N (torch's convention for a complex leaf), shapes and sums as
+    ``kspace_mask_grad``.  No autograd formula (double backward is not supported)."""
+    return rt.kspace_cmask_grad(x, g, n_dims, mask_channels, channels)
+
+
+@kspace_cmask_grad.register_fake
+def _kspace_cmask_grad_fake(x, g, n_dims, channels, mask_channels):
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    return x.new_empty(spatial if mask_channels == 1 else (mask_channels,) + spatial, dtype=torch.complex64)
+
+
+@torch.library.custom_op("texbias::kspace_cmask_learn", mutates_args=())
+def kspace_cmask_learn(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: int, pad: int = 0) -> torch.Tensor:
+    """``texbias::kspace_cmask`` (the same fused pass, bit for bit) for a learnable complex mask: autograd
+    with respect to the image and to the mask."""
+    return rt.kspace_cmask_learn(x, mask, n_dims, pad=pad, channels=channels)
+
+
+@kspace_cmask_learn.register_fake
+def _kspace_cmask_learn_fake(x, mask, n_dims, channels, pad=0):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+
+
+def _kspace_cmask_learn_setup(ctx, inputs, output):
+    x, mask, n_dims, channels, pad = inputs
+    ctx.save_for_backward(x, mask)
+    ctx.n_dims, ctx.channels, ctx.d = n_dims, channels, x.shape[-1]
+    ctx.cm = 1 if mask.dim() == n_dims else channels
+
+
+@torch.autograd.function.once_differentiable
+def _kspace_cmask_learn_backward(ctx, gy):
+    # image: the op with the conjugate flag; mask: conj(X) G / N per coefficient.  Only the gradients
+    # asked for are launched; once differentiable, as kspace_mask_learn.
+    x, mask = ctx.saved_tensors
+    g = gy[..., : ctx.d]
+    gx = gm = None
+    if ctx.needs_input_grad[0]:
+        gx = torch.ops.texbias.kspace_cmask(g, mask.detach(), ctx.n_dims, ctx.channels, 0, True)
+    if ctx.needs_input_grad[1]:
+        gm = torch.ops.texbias.kspace_cmask_grad(x, g, ctx.n_dims, ctx.channels, ctx.cm)
+    return gx, gm, None, None, None
+
+
+kspace_cmask_learn.register_autograd(_kspace_cmask_learn_backward, setup_context=_kspace_cmask_learn_setup)
 
 
 @torch.library.custom_op("texbias::shift_fourier", mutates_args=())

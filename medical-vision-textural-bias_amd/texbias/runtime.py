@@ -17,7 +17,7 @@ import torch
 
 from ._abi import TB_MAX_BATCH, TB_MAX_OPS, programs_array
 from ._lib import TexbiasError, check, lib
-from .kprog import Geometry, geometry, mask_op, split_program
+from .kprog import Geometry, cmask_op, geometry, mask_op, split_program
 
 _plans: Dict[Tuple[int, int, int, int], "Plan"] = {}
 _ws: "OrderedDict[Tuple[int, int], torch.Tensor]" = OrderedDict()
@@ -241,32 +241,43 @@ def mask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Op
     contiguous, on the image's device -- the kernels index it as M[Cm][H][W][D] with no copy, so
     nothing else is accepted.  A mask with ``requires_grad`` passes only with ``learnable`` (the
     ``kspace_mask_learn`` path, which has the gradient with respect to the mask)."""
+    return _mask_geometry("kspace_mask", torch.float32, x, mask, n_dims, channels, learnable)
+
+
+def cmask_geometry(x: torch.Tensor, mask: torch.Tensor, n_dims: int, channels: Optional[int] = None,
+                   learnable: bool = False) -> Tuple[int, int]:
+    """``mask_geometry`` for the complex mask of ``kspace_cmask`` (TB_OP_CMASK): the same shapes,
+    complex64 (interleaved re, im: what the kernels load), contiguous, on the image's device."""
+    return _mask_geometry("kspace_cmask", torch.complex64, x, mask, n_dims, channels, learnable)
+
+
+def _mask_geometry(what, dtype, x, mask, n_dims, channels, learnable):
     if not isinstance(x, torch.Tensor) or not isinstance(mask, torch.Tensor):
-        raise ValueError("kspace_mask: image and mask must be torch tensors")
+        raise ValueError(f"{what}: image and mask must be torch tensors")
     if n_dims < 1 or x.dim() < n_dims:
-        raise ValueError(f"kspace_mask: {n_dims} transformed axes on a {x.dim()}-d image")
+        raise ValueError(f"{what}: {n_dims} transformed axes on a {x.dim()}-d image")
     spatial = tuple(x.shape[x.dim() - n_dims:])
     lead = x.shape[: x.dim() - n_dims]
     if channels is None:
         channels = int(lead[-1]) if len(lead) else 1
     channels = int(channels)
     if channels < 1 or (int(np.prod(lead)) if len(lead) else 1) % channels:
-        raise ValueError(f"kspace_mask: {channels} channels do not divide the leading axes {tuple(lead)}")
+        raise ValueError(f"{what}: {channels} channels do not divide the leading axes {tuple(lead)}")
     if tuple(mask.shape) == spatial:
         cm = 1
     elif tuple(mask.shape) == (channels,) + spatial:
         cm = channels
     else:
-        raise ValueError(f"kspace_mask: mask shape {tuple(mask.shape)} is neither {spatial} nor "
+        raise ValueError(f"{what}: mask shape {tuple(mask.shape)} is neither {spatial} nor "
                          f"{(channels,) + spatial}")
-    if mask.dtype != torch.float32:
-        raise ValueError(f"kspace_mask: the mask must be float32, got {mask.dtype}")
+    if mask.dtype != dtype:
+        raise ValueError(f"{what}: the mask must be {str(dtype)[6:]}, got {mask.dtype}")
     if not mask.is_contiguous():
-        raise ValueError("kspace_mask: the mask must be contiguous")
+        raise ValueError(f"{what}: the mask must be contiguous")
     if mask.device != x.device:
-        raise ValueError(f"kspace_mask: mask on {mask.device}, image on {x.device}")
+        raise ValueError(f"{what}: mask on {mask.device}, image on {x.device}")
     if mask.requires_grad and not learnable:
-        raise ValueError("kspace_mask: a mask with requires_grad is not supported (no gradient w.r.t. the mask)")
+        raise ValueError(f"{what}: a mask with requires_grad is not supported (no gradient w.r.t. the mask)")
     return cm, channels
 
 
@@ -297,6 +308,34 @@ def _kspace_mask(x, mask, n_dims, pad, out, channels, learnable):
     return _kspace_filter_pass(x, n_dims, [prog] * (bc // channels), channels, out, pad)
 
 
+def kspace_cmask(x: torch.Tensor, mask: torch.Tensor, n_dims: int, pad: int = 0,
+                 out: Optional[torch.Tensor] = None, channels: Optional[int] = None,
+                 conj: bool = False) -> torch.Tensor:
+    """``kspace_mask`` with a complex64 mask (TB_OP_CMASK): a phase ramp (sub-voxel shift, motion), a
+    B0-like phase, a complex apodisation -- one fused round trip, no spectrum exported.  The ``.real``
+    of the reference makes it the multiplication of every stored coefficient by
+    (M[s(f)] + conj(M[s(-f)])) / 2.  ``conj``: use conj(mask), the adjoint of the same op (what the
+    autograd with respect to the image runs), read from the same buffer."""
+    return _kspace_cmask(x, mask, n_dims, pad, out, channels, False, conj)
+
+
+def kspace_cmask_learn(x: torch.Tensor, mask: torch.Tensor, n_dims: int, pad: int = 0,
+                       channels: Optional[int] = None) -> torch.Tensor:
+    """``kspace_cmask`` for a mask that may require grad (the forward of
+    ``torch.ops.texbias.kspace_cmask_learn``; the gradient with respect to the mask is ``kspace_cmask_grad``)."""
+    return _kspace_cmask(x, mask, n_dims, pad, None, channels, True, False)
+
+
+def _kspace_cmask(x, mask, n_dims, pad, out, channels, learnable, conj):
+    cm, channels = cmask_geometry(x, mask, n_dims, channels, learnable)
+    require_hip(x, "kspace_cmask")
+    hwd = geometry(x.shape[x.dim() - n_dims:]).hwd
+    lead = x.shape[: x.dim() - n_dims]
+    bc = int(np.prod(lead)) if len(lead) else 1
+    prog = [cmask_op(mask.data_ptr(), cm, hwd, conj=conj)]
+    return _kspace_filter_pass(x, n_dims, [prog] * (bc // channels), channels, out, pad)
+
+
 def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channels: int,
                      channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gradient of ``kspace_mask(x, M)`` with respect to the mask for an upstream gradient ``g`` (the
@@ -308,16 +347,29 @@ def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channel
     stream (``tb_kspace_mask_grad_f32``); every element is written once, so repeated calls agree bit
     for bit.  ``out``: a float32 contiguous tensor of the result's shape on the image's device to
     overwrite (it need not be zeroed)."""
+    return _mask_grad("kspace_mask_grad", torch.float32, x, g, n_dims, mask_channels, channels, out)
+
+
+def kspace_cmask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channels: int,
+                      channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``kspace_cmask(x, M)`` with respect to the complex mask, in torch.autograd's convention
+    for a complex leaf: dM[s(f)] = sum conj(FFT(x)(f)) FFT(g)(f) / N, complex64, with dM[s(-f)] =
+    conj(dM[s(f)]); its real part is ``kspace_mask_grad``'s.  Arguments, sums, strides and ``out``
+    (complex64 here) as ``kspace_mask_grad``; ``tb_kspace_cmask_grad_f32``."""
+    return _mask_grad("kspace_cmask_grad", torch.complex64, x, g, n_dims, mask_channels, channels, out)
+
+
+def _mask_grad(what, dtype, x, g, n_dims, mask_channels, channels, out):
     if not isinstance(x, torch.Tensor) or not isinstance(g, torch.Tensor):
-        raise ValueError("kspace_mask_grad: image and upstream gradient must be torch tensors")
+        raise ValueError(f"{what}: image and upstream gradient must be torch tensors")
     if n_dims < 1 or x.dim() < n_dims:
-        raise ValueError(f"kspace_mask_grad: {n_dims} transformed axes on a {x.dim()}-d image")
+        raise ValueError(f"{what}: {n_dims} transformed axes on a {x.dim()}-d image")
     if tuple(g.shape) != tuple(x.shape):
-        raise ValueError(f"kspace_mask_grad: upstream gradient {tuple(g.shape)} does not match the image {tuple(x.shape)}")
+        raise ValueError(f"{what}: upstream gradient {tuple(g.shape)} does not match the image {tuple(x.shape)}")
     if x.dtype != torch.float32 or g.dtype != torch.float32:
-        raise ValueError(f"kspace_mask_grad: float32 tensors expected, got {x.dtype} and {g.dtype}")
+        raise ValueError(f"{what}: float32 tensors expected, got {x.dtype} and {g.dtype}")
     if g.device != x.device:
-        raise ValueError(f"kspace_mask_grad: upstream gradient on {g.device}, image on {x.device}")
+        raise ValueError(f"{what}: upstream gradient on {g.device}, image on {x.device}")
     spatial = tuple(x.shape[x.dim() - n_dims:])
     lead = x.shape[: x.dim() - n_dims]
     if channels is None:
@@ -325,10 +377,10 @@ def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channel
     channels, cm = int(channels), int(mask_channels)
     bc = int(np.prod(lead)) if len(lead) else 1
     if channels < 1 or bc % channels:
-        raise ValueError(f"kspace_mask_grad: {channels} channels do not divide the leading axes {tuple(lead)}")
+        raise ValueError(f"{what}: {channels} channels do not divide the leading axes {tuple(lead)}")
     if cm != 1 and cm != channels:
-        raise ValueError(f"kspace_mask_grad: {cm} mask channels for {channels} image channels (1 or {channels})")
-    require_hip(x, "kspace_mask_grad")
+        raise ValueError(f"{what}: {cm} mask channels for {channels} image channels (1 or {channels})")
+    require_hip(x, what)
     geo = geometry(spatial)
     H, W, D = geo.hwd
 
@@ -343,18 +395,18 @@ def kspace_mask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channel
     g, gs = strided(g)
     shape = spatial if cm == 1 else (cm,) + spatial
     if out is None:
-        dm = torch.empty(shape, dtype=torch.float32, device=x.device)
+        dm = torch.empty(shape, dtype=dtype, device=x.device)
     else:
         dm = out
-        if (not isinstance(dm, torch.Tensor) or tuple(dm.shape) != shape or dm.dtype != torch.float32
+        if (not isinstance(dm, torch.Tensor) or tuple(dm.shape) != shape or dm.dtype != dtype
                 or not dm.is_contiguous() or dm.device != x.device):
-            raise ValueError(f"kspace_mask_grad: out must be a float32 contiguous {shape} tensor on {x.device}")
+            raise ValueError(f"{what}: out must be a {str(dtype)[6:]} contiguous {shape} tensor on {x.device}")
     plan = plan_for(x.device, H, W, D)
     with torch.cuda.device(x.device):
         ws = workspace(x.device, int(lib().tb_mask_grad_workspace_bytes(plan.handle, bc)))
-        check(lib().tb_kspace_mask_grad_f32(plan.handle, x.data_ptr(), xs, g.data_ptr(), gs, dm.data_ptr(), cm,
-                                            ws.data_ptr(), ws.numel(), bc // channels, channels, _stream(x.device)),
-              "tb_kspace_mask_grad_f32")
+        name = "tb_kspace_mask_grad_f32" if dtype == torch.float32 else "tb_kspace_cmask_grad_f32"
+        check(getattr(lib(), name)(plan.handle, x.data_ptr(), xs, g.data_ptr(), gs, dm.data_ptr(), cm, ws.data_ptr(),
+                                   ws.numel(), bc // channels, channels, _stream(x.device)), name)
     return dm
 
 
