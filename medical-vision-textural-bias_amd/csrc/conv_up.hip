@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "num_cu.h"
+#include "split_bf16.h"
 #include "texbias.h"
 
 namespace {
@@ -682,8 +683,230 @@ __global__ __launch_bounds__(NTH) void k_conv3d_fwd16(F16Args a) {  // 16-column
 }
 }  // namespace
 
-// (Round 6: the DMA-staged plane variant (439 vs 382 us) and the split-precision bf16 variant
-// k_conv16_x3 (no gain in the step) were measured, rejected and removed; DESIGN.md records them.)
+// (Round 6: the DMA-staged plane variant (439 vs 382 us) was measured, rejected and removed; the
+// split-precision bf16 variant k_conv16_x3 of that round (no gain in the step: its staging, not its
+// MFMAs, set its time) came back in round 15 as k_conv16_split below; DESIGN.md records both.)
+
+// ------------------------------------------------- the same layer in split precision on the bf16 matrix cores
+// f32 operands as three bf16 parts and six products per 32-k step (split_bf16.h): 96 matrix-core cycles
+// per 32 k where the f32 MFMA takes 256.  k = (tap, channel): a 32-k step q is two taps x 16 channels; lane
+// group g = lane >> 4 holds tap 2 q + (g >> 1) (tap 27: zero weights), channels 8 (g & 1) .. + 7, so its B
+// operand is 8 channels of ONE input position.  The staged planes are channel-innermost bf16,
+// [part][row][position][16] (position = x + 1, pitch 32 B: the lanes of a ds_read_b128 group hit distinct
+// banks), one 16-B read per part; the row holds W + 5 positions, a pitch of 8 dwords mod 32, so that the
+// staging writes of a half wave (4 channel quads x rows) spread over the banks.  The block's A operand
+// (14 steps x 3 parts) lives in registers for the kernel's life.  Staging: thread (channel quad, row,
+// x quad) loads four float4 (one per channel, 16 B along x) a step ahead, untouched until it splits them
+// at the LDS store: 12 ds_write_b64 (4 positions x 3 parts x 4 channels), rows and planes outside the
+// volume masked to zero there; idle threads write zeros to the row's spare positions -- no branch stands
+// around a load or a store.  Each wave takes one 16-column tile at a time (tiles wave, wave + 8, ..), the
+// B fragments of step q + 1 read ahead of step q's six MFMAs.  Block march, plane ring (4 slots and one
+// barrier per step where they fit, W <= 80; 3 slots up to W = 96), persistent shares: as k_conv3d_fwd16.
+namespace {
+struct X16Args {
+  const float* x;
+  const float* W;     // [16 m][16 c][27]
+  const float* bias;  // [16] or null
+  const float* add;   // [N][16][D][H][W] summed into y, or null
+  float* y;
+  int D, H, Wd;
+  int ZS, zlen, nyb;
+  int flip;           // 1: the input gradient, A = W[c][m][26 - t]
+  int persist, ncol;  // as F16Args
+  int64_t addsn;
+};
+
+constexpr int x16_pxp(int W) { return W + 5; }                     // positions per staged row (1 mod 4)
+constexpr size_t x16_slot(int W) { return (size_t)3 * 5 * x16_pxp(W) * 32; }  // bytes per plane slot
+
+template <int NXT, bool ADD, int NS>
+__global__ __launch_bounds__(512) void k_conv16_split(X16Args a) {
+  using tb::bf16x8;
+  constexpr int YB = 3, NR = YB + 2, NTH = 512, NWV = NTH / 64, W = 16 * NXT, W4 = 4 * NXT;
+  constexpr int RPB = x16_pxp(W) * 32, SPL = NR * RPB, SLOT = 3 * SPL;  // bytes: row, part, plane slot
+  constexpr int NTASK = 4 * NR * W4;  // staging tasks (channel quad, row, x quad)
+  static_assert(NTASK <= NTH && 2 * SPL + RPB < 65536 && (size_t)SLOT == x16_slot(W), "one task per thread");
+  extern __shared__ __attribute__((aligned(16))) char ring16[];  // [NS][3 parts][NR][W + 5][16] bf16
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int D = a.D, H = a.H;
+  for (int i = tid; i < NS * SLOT / 16; i += NTH) reinterpret_cast<uint4*>(ring16)[i] = make_uint4(0, 0, 0, 0);
+  // A: lane (m = l & 15, g = l >> 4), step q: tap 2 q + (g >> 1), channels 8 (g & 1) + j
+  const int li = lane & 15, g = lane >> 4, hi = g >> 1;
+  bf16x8 af[14][3];
+  const int wsm = a.flip ? 27 : 16 * 27, wsc = a.flip ? 16 * 27 : 27;  // W[m][c][t], flipped W[c][m][26 - t]
+  const float* wl = a.W + li * wsm + 8 * (g & 1) * wsc;
+#pragma unroll
+  for (int q = 0; q < 14; ++q) {
+    const int t = 2 * q + hi, tc = t < 27 ? t : 26;
+    const float* wq = wl + (a.flip ? 26 - tc : tc);
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = wq[j * wsc];
+    if (q == 13) {  // tap 27 does not exist: zero weights (the B operand there is tap 26's, finite)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = hi ? 0.f : v[j];
+    }
+    tb::split3(v, af[q][0], af[q][1], af[q][2]);
+  }
+  const float bm[4] = {a.bias ? a.bias[4 * g] : 0.f, a.bias ? a.bias[4 * g + 1] : 0.f,
+                       a.bias ? a.bias[4 * g + 2] : 0.f, a.bias ? a.bias[4 * g + 3] : 0.f};
+  int64_t s_beg, s_end;  // the block's steps, as in k_conv3d_fwd16
+  if (a.persist) {
+    const int64_t T = (int64_t)a.ncol * D;
+    s_beg = T * blockIdx.x / gridDim.x, s_end = T * (blockIdx.x + 1) / gridDim.x;
+  } else {
+    int b = (int)blockIdx.x;
+    const int zs = b % a.ZS;
+    b /= a.ZS;
+    const int zb = zs * a.zlen;
+    s_beg = (int64_t)b * D + zb, s_end = (int64_t)b * D + min(D, zb + a.zlen);
+  }
+  // this thread's staging task; threads past the last task load the sample's first floats and write zeros
+  // over the spare positions W + 1 .. W + 4 of row 0 (W + 1 is the right halo: zero anyway)
+  const bool act = tid < NTASK;
+  const int cq = tid & 3, rr = act ? (tid >> 2) % NR : 0, q4 = act ? (tid >> 2) / NR : 0;
+  const int lof = act ? rr * RPB + (4 * q4 + 1) * 32 + cq * 8 : (W + 1) * 32;
+  // B lane base: position li (+ tx), channel half g & 1
+  const int lb = li * 32 + 16 * (g & 1);
+  constexpr int NT = YB * NXT;                // tiles per step
+  constexpr int NIT = (NT + NWV - 1) / NWV;   // tiles per wave
+  for (int64_t sg = s_beg; sg < s_end;) {
+    const int col = (int)(sg / D), z0 = (int)(sg - (int64_t)col * D);
+    const int z1 = (int)min((int64_t)D, z0 + (s_end - sg));
+    sg += z1 - z0;
+    const int yb = col % a.nyb, n = col / a.nyb;
+    const int y0 = yb * YB;
+    const int64_t plane = (int64_t)H * W, plane4 = plane / 4, chq = (int64_t)D * plane4;
+    const float4* xb = reinterpret_cast<const float4*>(a.x + (int64_t)n * 16 * D * plane);
+    const int yi = y0 - 1 + rr;
+    const bool rowok = act && yi >= 0 && yi < H;
+    // per-lane byte offsets (32 bits: the host keeps a sample below 2 GiB) on wave-uniform bases
+    const unsigned gof = rowok ? (unsigned)(16 * (4 * cq * chq) + 4 * ((int64_t)yi * W + 4 * q4)) : 0u;  // clamped into the tensor
+    const unsigned lo = (unsigned)(4 * ((int64_t)4 * g * D * plane + li));  // output: rows m = 4 g + r, column li
+    float4 rg[4];
+    auto load = [&](int zi) {  // nothing conditional; zeroed by the mask at the store
+      const char* src = reinterpret_cast<const char*>(xb + (int64_t)(zi < 0 ? 0 : zi >= D ? D - 1 : zi) * plane4);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) rg[c] = *reinterpret_cast<const float4*>(src + 16 * c * chq + gof);
+    };
+    auto store = [&](int zi) {
+      char* d = ring16 + ((zi + NS) % NS) * SLOT + lof;
+      const unsigned m = 0u - (unsigned)(rowok && zi >= 0 && zi < D);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          v[c] = __uint_as_float(__float_as_uint(e == 0 ? rg[c].x : e == 1 ? rg[c].y : e == 2 ? rg[c].z : rg[c].w) & m);
+        unsigned p[3][2];
+        tb::split3_pk(v[0], v[1], p[0][0], p[1][0], p[2][0]);
+        tb::split3_pk(v[2], v[3], p[0][1], p[1][1], p[2][1]);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) *reinterpret_cast<uint2*>(d + s * SPL + e * 32) = make_uint2(p[s][0], p[s][1]);
+      }
+    };
+    __syncthreads();
+    load(z0 - 1);
+    store(z0 - 1);
+    load(z0);
+    store(z0);
+    load(z0 + 1);
+    store(z0 + 1);
+    // every start-up load (weights, bias, the first planes) retired here: no vmcnt(0) ahead of a step's MFMAs
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+    float* yb0 = a.y + (int64_t)n * 16 * D * plane;
+    const float* ab0 = ADD ? a.add + (int64_t)n * (a.addsn ? a.addsn : 16 * D * plane) : nullptr;
+    // step z: fetch plane z + 2 (registers) | per tile: MFMAs over planes z - 1 .. z + 1, output stores |
+    // (3 slots: barrier) | plane z + 2 split into the slot plane z - 2 (3 slots: z - 1) held | barrier
+    for (int z = z0; z < z1; ++z) {
+      load(z + 2);
+      int hv = hi;  // opaque: the per-step B offsets it selects are recomputed, not kept in 14 registers
+      asm volatile("" : "+v"(hv));
+      int sb[3];  // byte offsets of planes z - 1, z, z + 1
+#pragma unroll
+      for (int tz = 0; tz < 3; ++tz) sb[tz] = ((z + tz + NS - 1) % NS) * SLOT;
+      // the wave's last tile is stored after the plane's LDS store: the wait for the plane loads then has
+      // only stores a tile old behind it
+      tb::f32x4s cl = {0.f, 0.f, 0.f, 0.f};
+      float avl[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int t = wave + NWV * it;
+        if (t < NT) {
+          const int yy = t / NXT, x0 = 16 * (t - yy * NXT);
+          // ADD: the tile's `add` values fetched ahead of its MFMAs, summed at its stores
+          const int64_t ou = ((int64_t)z * plane + (int64_t)min(y0 + yy, H - 1) * W + x0) * 4;
+          float av[4];
+          if constexpr (ADD) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              av[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(ab0) + ou + 4 * r * D * plane + lo);
+          }
+          const char* rb = ring16 + yy * RPB + x0 * 32 + lb;
+          bf16x8 bq[2][3];
+          auto ldb = [&](int q, bf16x8 (&b)[3]) {  // read in the order the products take them: parts 1, 2, 0
+            const int t0 = 2 * q, t1 = 2 * q + 1 < 27 ? 2 * q + 1 : 26;
+            const int c0 = ((t0 / 3) % 3) * RPB + (t0 % 3) * 32, c1 = ((t1 / 3) % 3) * RPB + (t1 % 3) * 32;
+            const int o = t0 / 9 == t1 / 9 ? sb[t0 / 9] + (hv ? c1 : c0) : hv ? sb[t1 / 9] + c1 : sb[t0 / 9] + c0;
+            b[1] = *reinterpret_cast<const bf16x8*>(rb + o + SPL);
+            b[2] = *reinterpret_cast<const bf16x8*>(rb + o + 2 * SPL);
+            b[0] = *reinterpret_cast<const bf16x8*>(rb + o);
+          };
+          tb::f32x4s c = {0.f, 0.f, 0.f, 0.f}, cs = c;  // leading / small products; the bias joins at the store
+          ldb(0, bq[0]);
+#pragma unroll
+          for (int q = 0; q < 14; ++q) {
+            if (q + 1 < 14) ldb(q + 1, bq[(q + 1) & 1]);
+            tb::mfma_split6(af[q], bq[q & 1], c, cs);
+          }
+          c += cs;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) c[r] += bm[r];
+          // schedule: (the `add` loads,) step q + 1's three reads, then step q's six MFMAs
+          if constexpr (ADD) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+          for (int q = 0; q < 13; ++q) {
+            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+          if constexpr (ADD) {  // waited for on every path (a skippable wait comes back ahead of the next loads)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(av[r]));
+          }
+          if (it == NIT - 1) {
+            cl = c;
+            if constexpr (ADD) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) avl[r] = av[r];
+            }
+          } else if (y0 + yy < H) {  // C: column x = li, rows m = 4 g + r
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              *reinterpret_cast<float*>(reinterpret_cast<char*>(yb0) + ou + 4 * r * D * plane + lo) = ADD ? c[r] + av[r] : c[r];
+          }
+        }
+      }
+      if constexpr (NS == 3) __syncthreads();
+      store(z + 2);  // unconditionally (after the last step a dead slot)
+      {
+        const int t = wave + NWV * (NIT - 1);
+        const int yy = t / NXT, x0 = 16 * (t - yy * NXT);
+        if (t < NT && y0 + yy < H) {
+          const int64_t ou = ((int64_t)z * plane + (int64_t)(y0 + yy) * W + x0) * 4;
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<float*>(reinterpret_cast<char*>(yb0) + ou + 4 * r * D * plane + lo) = ADD ? cl[r] + avl[r] : cl[r];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+}  // namespace
 
 
 // Conv3d(16 -> 16, 3, stride 1, padding 1) forward: x [N][16][D][H][W] -> y [N][16][D][H][W], W % 16 == 0,
@@ -706,10 +929,45 @@ int tb_conv3d_fwd16_dgrad_f32(const float* gy, const float* W, const float* add,
   return fwd16_call(gy, W, nullptr, add, dx, N, D, H, Wd, 1, stream, add_sn);
 }
 
+static int split16_call(const float* x, const float* W, const float* bias, const float* add, float* y, int N, int D,
+                        int H, int Wd, int flip, void* stream, int64_t add_sn) {
+  X16Args a{};
+  a.x = x, a.W = W, a.bias = bias, a.add = add, a.y = y, a.D = D, a.H = H, a.Wd = Wd;
+  a.flip = flip;
+  a.addsn = add_sn;
+  a.nyb = (H + 2) / 3;
+  const int NS = 4 * x16_slot(Wd) <= 163840 ? 4 : 3;  // 4-slot plane ring where it fits (W <= 80)
+  const size_t lds = NS * x16_slot(Wd);
+  a.zlen = zseg(D, N * a.nyb, 1, 2);  // 8 waves at 2 per SIMD: one block per CU
+  a.ZS = (D + a.zlen - 1) / a.zlen;
+  void (*kern)(X16Args) = nullptr;
+#define TB_X16(NX, S) \
+  case NX: kern = add ? k_conv16_split<NX, true, S> : k_conv16_split<NX, false, S>; break;
+  switch (Wd / 16) {
+    TB_X16(1, 4) TB_X16(2, 4) TB_X16(3, 4) TB_X16(4, 4) TB_X16(5, 4) TB_X16(6, 3)
+    default: return TB_ERR_UNSUPPORTED_SIZE;
+  }
+#undef TB_X16
+  if (NS != (Wd <= 80 ? 4 : 3)) return TB_ERR_UNSUPPORTED_SIZE;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
+      hipSuccess)
+    return TB_ERR_HIP;
+  // persistent shares when the (n, yb, z segment) grid leaves CUs idle, as for k_conv3d_fwd16
+  a.ncol = N * a.nyb;
+  unsigned nblk = (unsigned)(N * a.nyb * a.ZS);
+  a.persist = (int64_t)a.ncol * D >= 8LL * tb::num_cu() && nblk % tb::num_cu() != 0;
+  if (a.persist) nblk = (unsigned)tb::num_cu();
+  hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, reinterpret_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+}
+
 static int fwd16_call(const float* x, const float* W, const float* bias, const float* add, float* y, int N, int D, int H,
                       int Wd, int flip, void* stream, int64_t add_sn) {
   if (!x || !W || !y || N < 1 || D < 1 || H < 1 || Wd < 1) return TB_ERR_INVALID_ARG;
   if (Wd % 16 != 0 || Wd > 128 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return TB_ERR_UNSUPPORTED_SIZE;
+  // rows whose split-bf16 plane ring fits the LDS (W <= 96), samples below 2 GiB (32-bit byte offsets):
+  // k_conv16_split; the others stay on the f32 MFMA
+  if (3 * x16_slot(Wd) <= 163840 && (int64_t)16 * D * H * Wd < (1LL << 29)) return split16_call(x, W, bias, add, y, N, D, H, Wd, flip, stream, add_sn);
   // output rows per block (C3, W = 80: YB 2 / 3 / 4 = 478 / 419 / 482 us -- the YB x 5 tiles of a step
   // over 4 waves x 2 chains: 10 of 16, 15 of 16, 20 of 24 slots used; YB = 2's second block per CU did not
   // make up for it): only YB = 3 is instantiated
