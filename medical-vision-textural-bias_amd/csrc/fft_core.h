@@ -23,6 +23,7 @@
 //     the inverse DIT consumes that order directly, so no permutation pass exists.
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
 #include "texbias.h"
 
@@ -618,10 +619,16 @@ TB_HD bool layer_in(const tb_op& op, int e2) {
 TB_HD cf spike_target(const tb_op& op, cf kf) {
   float ph = op.f[1];
   if (ph != ph) {  // NaN -> keep the coefficient's own phase (angle(0) = 0)
-    const float m2 = kf.x * kf.x + kf.y * kf.y;
-    if (m2 > 0.f) {
-      const float inv = 1.f / f32_sqrt(m2);
-      return mk(op.f[0] * kf.x * inv, op.f[0] * kf.y * inv);
+    // the unit phasor of kf scaled by a power of two to max(|re|, |im|) in [0.5, 1): its square neither
+    // underflows (|kf| < 2^-75 took phase 0) nor overflows (|kf| >= 2^64 zeroed the spike); the same bits
+    // as the unscaled form wherever that one stays normal
+    const float mx = fmaxf(fabsf(kf.x), fabsf(kf.y));
+    if (mx > 0.f) {
+      int ex;
+      (void)frexpf(mx, &ex);
+      const float sx = ldexpf(kf.x, -ex), sy = ldexpf(kf.y, -ex);
+      const float inv = 1.f / f32_sqrt(sx * sx + sy * sy);
+      return mk(op.f[0] * sx * inv, op.f[0] * sy * inv);
     }
     return mk(op.f[0], 0.f);
   }

@@ -266,6 +266,7 @@ __global__ __launch_bounds__(BAND_NT) __attribute__((amdgpu_waves_per_eu(NT2 * K
       mx = wave_max(mx);
       int ex;
       (void)frexpf(mx, &ex);  // mx < 2^ex (0 for a zero strip)
+      ex = ex < SPLIT_EX_MIN ? SPLIT_EX_MIN : ex;  // a strip of tiny values: 2^(14 - ex) stays finite
       ssc = ldexpf(1.f, 14 - ex);
       wsc = ldexpf(1.f, ex - 14) * (1.f / BAND_FWD16_TSCALE);
     }
@@ -339,6 +340,17 @@ __global__ __launch_bounds__(BAND_NT) __attribute__((amdgpu_waves_per_eu(NT2 * K
           }
         }
       } else {
+        // The row's first value c comes off every element before the sums and returns as c D at kd = 0 (the
+        // cosines of a kd != 0 sum to 0 over d).  On a row of raw intensities (1000 + noise) the products
+        // s_d cos are ~2000 each and cancel: their roundings, not the data, set the error of every kd != 0
+        // coefficient (1e-4 of a coefficient of 19 at 31 x 17 x 30, which a kept-phase spike turns into 1e-4
+        // rad); without c they are of the noise's size.  t_d = x(D - d) - x(d) never held c.
+        // Only this run-time-D body does it.  The compiled-D bodies above (D = 128 / 155 with <= 16 kd columns,
+        // the split-f16 one among them) still sum the raw rows and have the same weakness: disk + in-box
+        // kept-phase spike on 1000 + noise data at 24 x 20 x 155 comes out 8.8 times max(e_ref32, 1e-6 scale),
+        // where tests/test_gpu_value_classes.py asks 4 of the cells it runs (it runs no in-box spike there).
+        // In the split-f16 body the centred s_d can reach 4 max|x|, so its scale would have to give up a bit.
+        const float c0 = row[0];
         for (int k0 = 0; k0 < KSd; k0 += 4) {
           float sv[4], tv[4];
 #pragma unroll
@@ -346,8 +358,8 @@ __global__ __launch_bounds__(BAND_NT) __attribute__((amdgpu_waves_per_eu(NT2 * K
             const int d = 4 * (k0 + q) + l4;
             const bool has = d < Ld;
             const bool pair = d >= 1 && 2 * d < D;
-            const float xa = has ? row[d] : 0.f;
-            const float xm = pair ? row[D - d] : 0.f;
+            const float xa = has ? row[d] - c0 : 0.f;
+            const float xm = pair ? row[D - d] - c0 : 0.f;
             sv[q] = xa + xm;
             tv[q] = pair ? xm - xa : 0.f;
           }
@@ -362,6 +374,10 @@ __global__ __launch_bounds__(BAND_NT) __attribute__((amdgpu_waves_per_eu(NT2 * K
             }
           }
         }
+        // kd = 0 (column 0 of tile 0: lanes with l15 == 0) of rows 4 l4 + j gets its row's c D back
+        const float cd = l15 == 0 ? (float)D : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) accc[0][j] = fmaf(xs[(4 * l4 + j) * P], cd, accc[0][j]);
       }
     }
     // 4. W product: rows w = w0 + 4 (l/16) + j of the strip; rows >= W weigh 0
@@ -1221,6 +1237,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(VT == 1
       m = wave_max(m);
       int ex;
       (void)frexpf(m, &ex);  // m < 2^ex
+      ex = ex < SPLIT_EX_MIN ? SPLIT_EX_MIN : ex;
       const float sv = ldexpf(1.f, 15 - ex), inv = ldexpf(1.f, ex - 15) * (1.f / BAND_T16_SCALE);
       h16x8 ah[2 * VT], al[2 * VT];
 #pragma unroll

@@ -214,6 +214,7 @@ __global__ __launch_bounds__(WRAP_NT) __attribute__((amdgpu_waves_per_eu(NTO <= 
     // per-unit power of two: max |scaled| < 2^14 (f16 hi parts in range, lo parts normal)
     int ex;
     (void)frexpf(wave_max(mx), &ex);
+    ex = ex < SPLIT_EX_MIN ? SPLIT_EX_MIN : ex;
     const float sx = ldexpf(1.f, 14 - ex), inv = ldexpf(1.f, ex - 14) * (1.f / WRAP_K_SCALE);
 #pragma unroll
     for (int r = 0; r < 4; ++r)

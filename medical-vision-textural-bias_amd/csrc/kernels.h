@@ -165,6 +165,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return wave_reduce(v, [](float x, float y) { return fmaxf(x, y); });
 }
 
+// Lower bound of the exponent ex (max |x| < 2^ex) from which the split-f16 kernels take their per-strip /
+// per-unit power-of-two scale 2^(14 - ex) or 2^(15 - ex).  Unbounded, a unit whose largest value is below
+// 2^-114 (2^-113) but not 0 gets the scale 2^128 = inf, and inf x 0 = NaN reaches the whole output.  -103 is
+// the lowest bound at which every inverse scale is still a normal float (2^(ex - 15) x 2^-8 = 2^-126 in
+// k_band_inv16).  A unit with max |x| >= 2^-104 is scaled as before; a smaller one is scaled by 2^117 (2^118)
+// and its f16 parts end at the f16 subnormal spacing 2^-24: it loses what lies below 2^-141.
+constexpr int SPLIT_EX_MIN = -103;
+
 // Three-operand min / max (v_min3_f32 / v_max3_f32) without the canonicalising v_max_f32 x, x, x that
 // fminf / fmaxf put on every operand the compiler cannot prove canonical (loop-carried running values,
 // packed-math results): one instruction per two values folded in.  For the running min / max of
