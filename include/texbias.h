@@ -410,7 +410,8 @@ int tb_conv3d_mfma_dgrad_f32(const float* gy, const float* W, const float* add, 
                              int D, int H, int Wd, void* stream);
 
 /*
- * The U-Net's channel-deep convolutions as implicit GEMMs on the f32 matrix cores (csrc/conv_gemm.hip;
+ * The U-Net's channel-deep convolutions as implicit GEMMs on the matrix cores (f32 MFMA for M <= 64,
+ * split precision on the bf16 MFMA -- csrc/split_bf16.h, results closer to float64 -- above; csrc/conv_gemm.hip;
  * train step of 10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-243, MONAI UNet module tree
  * source_code/test.ipynb:754-1010 -- the stride-2 entries 16 -> 32 .. 64 -> 128, the 128/256-channel
  * bottom unit, the ConvTranspose3d ups and every one of their input gradients, which MIOpen/CK ran at

@@ -1,4 +1,4 @@
-// conv_gemm.hip -- the U-Net's channel-deep convolutions as implicit GEMMs on the f32 matrix cores.
+// conv_gemm.hip -- the U-Net's channel-deep convolutions as implicit GEMMs on the matrix cores.
 //
 // The reference's MONAI UNet (10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-199; module tree
 // source_code/test.ipynb:754-1010) has, besides the full-resolution layers of conv_up.hip, the
@@ -27,6 +27,12 @@
 // (each lane's positions fixed for the block).  Small GEMMs split k over nsplit slices into float
 // partials summed by k_cg_reduce (which adds bias / add and scatters to the output grid).  Blocks are
 // numbered so that the m tiles of one position tile land on one XCD (its L2 serves the X~ re-reads).
+//
+// The 128 x 128 tile (M > 64) runs in split precision on the bf16 matrix cores (SplitTile of gemm_core.h,
+// 512 threads): k_cg_pack writes A as its three bf16 parts, which the A stager moves to LDS as they are, and
+// the gathered X~ is split at its LDS store; bias, `add`, the partials and k_cg_reduce stay f32.  The
+// 32 x 128 and 64 x 64 tiles measured no faster that way on any C3 layer (they are held by the gather, not by
+// the f32 MFMA rate) and stay on the f32 Tile (profiles/r17/README.md).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,7 +48,7 @@ using namespace tb::gemm;
 
 struct CGArgs {
   const float* x;
-  const float* A;
+  const void* A;  // packed by k_cg_pack: f32, or the three bf16 part images
   const float* bias;
   const float* add;
   float* y;
@@ -59,6 +65,7 @@ struct CGArgs {
   int nsplit, kper, mtiles, ptiles, ncls;
   int kind;  // taps: 0 = 3x3x3 (tz - 1, ty - 1, tx - 1), 1 = 1x1x1, 2 = sub-pixel class (parity bits = class)
   int64_t aoff[8];
+  int64_t apart;  // elements between the bf16 part images of the packed A (split tiles)
   int Kc[8], Tc[8];
 };
 
@@ -79,15 +86,24 @@ __host__ __device__ inline void tap_of(int kind, int cls, int j, int& dz, int& d
   }
 }
 
-template <int BM, int BP, int WGM>
-__global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
-  using TileT = Tile<BM, BP, WGM>;
-  constexpr int NPOS = BP / 64;          // gather positions per lane
-  constexpr int AQ = BM * KC / 4 / NTH;  // A float4 per thread per stage
+// SP: the split-precision tile (SplitTile, NT threads; A read as the three bf16 part images k_cg_pack wrote,
+// the gathered X~ split at its LDS store); otherwise the f32 Tile on NT = NTH threads and an f32 A.
+template <int BM, int BP, int WGM, int NT, bool SP>
+__global__ __launch_bounds__(NT) void k_conv_gemm(const CGArgs a) {
+  using TileT = std::conditional_t<SP, SplitTile<BM, BP, WGM, NT>, Tile<BM, BP, WGM>>;
+  using LdsT = std::conditional_t<SP, char, float>;
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  static_assert(SP || NT == NTH, "the f32 tile runs on NTH threads");
+  constexpr int PG = NT / 256;                         // position groups: wave w gathers k octet w & 3 of group w >> 2
+  constexpr int NPOS = BP / (64 * PG);                 // gather positions per lane
+  constexpr int AQ = SP ? (BM * 4 + NT - 1) / NT       // A (row, k octet) items per thread per stage, three parts each
+                        : BM * KC / 4 / NT;            // A float4 per thread per stage
   static_assert(NPOS >= 1 && AQ >= 1, "tile");
-  extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  LdsT* const lds_dyn = reinterpret_cast<LdsT*>(lds_raw);
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wk = w & 3, pg = w >> 2;
   int b = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   const int mt = b % a.mtiles;
   b /= a.mtiles;
@@ -95,20 +111,19 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
   b /= a.ptiles;
   const int split = b % a.nsplit, cls = b / a.nsplit;
   const int T = a.Tc[cls], K = a.Kc[cls];
-  const float* __restrict__ A = a.A + a.aoff[cls];
   const int Cin = a.Cin;
   const int k_beg = split * a.kper;
   const int k_end = min(K, k_beg + a.kper);
   const int m0 = mt * BM, p0 = pt * BP;
   const int IHW = a.IH * a.IW;
 
-  // gather positions: lane + 64 i of the tile; byte offset of the tap-(0,0,0) voxel of channel 0 and the
-  // per-tap validity bits
+  // gather positions: lane + 64 (PG i + pg) of the tile; byte offset of the tap-(0,0,0) voxel of channel 0
+  // and the per-tap validity bits
   int xo[NPOS];
   uint32_t vm[NPOS];
 #pragma unroll
   for (int i = 0; i < NPOS; ++i) {
-    const int p = p0 + lane + 64 * i;
+    const int p = p0 + lane + 64 * (PG * i + pg);
     const bool ok = p < a.P;
     int t = ok ? p : 0;
     const int ox = t % a.OW;
@@ -136,11 +151,11 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
 
   // the stagers' two register slots (gemm_core.h); stage s holds k rows k_beg + 32 s .. + 31
   float rb[2][NPOS][8];
-  f32x4 ra[2][AQ];
+  std::conditional_t<SP, u32x4[2][AQ][3], f32x4[2][AQ]> ra;
   auto gather = [&](auto SL, int k0) {
     constexpr int sl = decltype(SL)::value;
-    // rows k0 + 8 w .. + 7: channels c .. c + 7 of tap t (Cin % 8 == 0)
-    const int k = k0 + 8 * w;
+    // rows k0 + 8 wk .. + 7: channels c .. c + 7 of tap t (Cin % 8 == 0)
+    const int k = k0 + 8 * wk;
     const int t = k / Cin, c = k - t * Cin;
     const bool kin = k < k_end;
     int dz, dy, dx, wi;
@@ -156,16 +171,32 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
         rb[sl][i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, vo, soff + r * xsc4, 0));
     }
   };
-  const uint32_t abytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(4 * (int64_t)a.M * K));
-  const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)abytes, 0x00020000);
+  // A of the class: f32 [M][K], or three bf16 images [M][K] a.apart elements apart (range: to the end of
+  // the third image's rows of this class)
+  const int esz = SP ? 2 : 4;
+  const char* Ab = reinterpret_cast<const char*>(a.A) + esz * a.aoff[cls];
+  const int apart2 = __builtin_amdgcn_readfirstlane((int)(2 * a.apart));
+  const uint32_t abytes =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(esz * (int64_t)a.M * K + (SP ? 2 * (int64_t)apart2 : 0)));
+  const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(Ab), 0, (int)abytes, 0x00020000);
   auto aload = [&](auto SL, int k0) {
     constexpr int sl = decltype(SL)::value;
 #pragma unroll
     for (int u = 0; u < AQ; ++u) {
-      const int q4 = tid + NTH * u, row = q4 % BM, kq = k0 + 4 * (q4 / BM);
-      const int m = m0 + row;
-      const int vo = (m < a.M && kq < k_end) ? 4 * (m * K + kq) : (int)0x80000000;
-      ra[sl][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ar, vo, 0, 0));
+      if constexpr (SP) {
+        const int it = tid + NT * u, row = it % BM, kq = k0 + 8 * (it / BM);
+        const int m = m0 + row;
+        const bool v = (BM * 4 % NT == 0 || it < BM * 4) && m < a.M && kq < k_end;
+        const int vo = v ? 2 * (m * K + kq) : (int)0x80000000;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+          ra[sl][u][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ar, vo, p * apart2, 0));
+      } else {
+        const int q4 = tid + NT * u, row = q4 % BM, kq = k0 + 4 * (q4 / BM);
+        const int m = m0 + row;
+        const int vo = (m < a.M && kq < k_end) ? 4 * (m * K + kq) : (int)0x80000000;
+        ra[sl][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ar, vo, 0, 0));
+      }
     }
   };
   auto load = [&](auto SL, int s) {  // masked by k < k_end: past the slice both read zeros
@@ -174,17 +205,40 @@ __global__ __launch_bounds__(NTH) void k_conv_gemm(const CGArgs a) {
   };
   auto store = [&](auto SL) {
     constexpr int sl = decltype(SL)::value;
-    float* L = lds_dyn + sl * TileT::LBUF;
+    if constexpr (SP) {
+      char* L = lds_dyn + sl * TileT::LBUF;
 #pragma unroll
-    for (int u = 0; u < AQ; ++u) {
-      const int q4 = tid + NTH * u, row = q4 % BM, c4 = q4 / BM;
-      *reinterpret_cast<f32x4*>(L + row * RS + 4 * c4) = ra[sl][u];
-    }
+      for (int u = 0; u < AQ; ++u) {
+        const int it = tid + NT * u;
+        if (BM * 4 % NT == 0 || it < BM * 4) {
 #pragma unroll
-    for (int i = 0; i < NPOS; ++i) {
-      float* d = L + (BM + lane + 64 * i) * RS + 8 * w;
-      *reinterpret_cast<f32x4*>(d) = f32x4{rb[sl][i][0], rb[sl][i][1], rb[sl][i][2], rb[sl][i][3]};
-      *reinterpret_cast<f32x4*>(d + 4) = f32x4{rb[sl][i][4], rb[sl][i][5], rb[sl][i][6], rb[sl][i][7]};
+          for (int p = 0; p < 3; ++p)
+            *reinterpret_cast<u32x4*>(L + p * TileT::IMG + TileT::a_off(it % BM, it / BM)) = ra[sl][u][p];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NPOS; ++i) {
+        unsigned q[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tb::split3_pk(rb[sl][i][2 * j], rb[sl][i][2 * j + 1], q[0][j], q[1][j], q[2][j]);
+        char* d = L + TileT::b_off(lane + 64 * (PG * i + pg), wk);
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+          *reinterpret_cast<u32x4*>(d + p * TileT::IMG) = u32x4{q[p][0], q[p][1], q[p][2], q[p][3]};
+      }
+    } else {
+      float* L = lds_dyn + sl * TileT::LBUF;
+#pragma unroll
+      for (int u = 0; u < AQ; ++u) {
+        const int q4 = tid + NT * u, row = q4 % BM, c4 = q4 / BM;
+        *reinterpret_cast<f32x4*>(L + row * RS + 4 * c4) = ra[sl][u];
+      }
+#pragma unroll
+      for (int i = 0; i < NPOS; ++i) {
+        float* d = L + (BM + lane + 64 * i) * RS + 8 * w;
+        *reinterpret_cast<f32x4*>(d) = f32x4{rb[sl][i][0], rb[sl][i][1], rb[sl][i][2], rb[sl][i][3]};
+        *reinterpret_cast<f32x4*>(d + 4) = f32x4{rb[sl][i][4], rb[sl][i][5], rb[sl][i][6], rb[sl][i][7]};
+      }
     }
   };
 
@@ -259,7 +313,10 @@ __global__ __launch_bounds__(256) void k_cg_reduce(const CGArgs a) {
 // Packed A operands, k tap-major: A_cls[m][j Cin + c] = W(m, c, tap_j of cls).  mode 0 (Conv3d, W
 // [M][Cin][T]): W[m][c][widx]; mode 1 (input gradient of a stride-1 conv whose weight is Wl [Cin][M][T]):
 // Wl[c][m][T - 1 - widx]; mode 2 (sub-pixel classes, Wt [Cin][M][27]): Wt[c][m][widx].
-__global__ __launch_bounds__(256) void k_cg_pack(const float* __restrict__ W, float* __restrict__ out, int mode,
+// SP: written as its three bf16 parts (split_bf16.h), image p at out + p total elements -- the split tile's A
+// stager then moves 16-B octets to LDS with no conversion.
+template <bool SP>
+__global__ __launch_bounds__(256) void k_cg_pack(const float* __restrict__ W, void* __restrict__ out, int mode,
                                                  int64_t total, const CGArgs a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -276,16 +333,32 @@ __global__ __launch_bounds__(256) void k_cg_pack(const float* __restrict__ W, fl
   if (mode == 0) v = W[((int64_t)m * Cin + c) * TW + wi];
   else if (mode == 1) v = W[((int64_t)c * M + m) * TW + (TW - 1 - wi)];
   else v = W[((int64_t)c * M + m) * 27 + wi];
-  out[i] = v;
+  if constexpr (SP) {
+    unsigned p0, p1, p2;
+    tb::split3_pk(v, 0.f, p0, p1, p2);
+    uint16_t* o = static_cast<uint16_t*>(out) + i;
+    o[0] = (uint16_t)p0, o[total] = (uint16_t)p1, o[2 * total] = (uint16_t)p2;
+  } else {
+    static_cast<float*>(out)[i] = v;
+  }
 }
 
 struct Plan {
   CGArgs a;
   int BM, BP, WGM;
+  bool split;  // the split-precision tile (its packed A is three bf16 images, 6 B per element)
   size_t pack_floats, part_floats;
+  size_t pack_bytes() const { return (pack_floats * (split ? 6 : 4) + 255) & ~size_t(255); }
+  size_t ws_bytes() const { return pack_bytes() + 4 * ((part_floats + 63) & ~size_t(63)) + 256; }
 };
 
-inline size_t align_floats(size_t n) { return (n + 63) & ~size_t(63); }
+// The tiles: M <= 32 -> 32 x 128; M <= 64 -> 64 x 64; else 128 x 128 on 512 threads (eight waves of 64 x 32:
+// its two split stage buffers are 120 KB, one block per CU, so the block itself brings two waves per SIMD).
+struct TileCfg {
+  int BM, BP, WGM, NT;
+  bool split;
+};
+constexpr TileCfg kTiles[3] = {{32, 128, 1, NTH, false}, {64, 64, 2, NTH, false}, {128, 128, 2, 512, true}};
 
 // Fill the geometry and tiling of a call (no device pointers).  Returns TB_OK or an error code.
 int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride, int ksize, Plan& pl) {
@@ -321,10 +394,10 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
   a.ysc = a.ymul == 2 ? 8 * a.OD * a.OH * a.OW : a.OD * a.OH * a.OW;
   if ((int64_t)N * M * a.ysc >= (int64_t)1 << 31) return TB_ERR_UNSUPPORTED_SIZE;
   a.P = N * a.OD * a.OH * a.OW;
-  // tile: M <= 32 -> 32 x 128; M <= 64 -> 64 x 64; else 128 x 128
-  static const int cfg[3][3] = {{32, 128, 1}, {64, 64, 2}, {128, 128, 2}};
-  const int tile = M <= 32 ? 0 : (M <= 64 ? 1 : 2);
-  pl.BM = cfg[tile][0], pl.BP = cfg[tile][1], pl.WGM = cfg[tile][2];
+  const TileCfg& tc = kTiles[M <= 32 ? 0 : (M <= 64 ? 1 : 2)];
+  pl.BM = tc.BM, pl.BP = tc.BP, pl.WGM = tc.WGM, pl.split = tc.split;
+  a.apart = (int64_t)pl.pack_floats;
+  if (6 * (int64_t)pl.pack_floats >= (int64_t)1 << 31) return TB_ERR_UNSUPPORTED_SIZE;
   a.mtiles = (M + pl.BM - 1) / pl.BM;
   a.ptiles = (a.P + pl.BP - 1) / pl.BP;
   int Kmax = 0;
@@ -332,7 +405,7 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
   // split k to minimise (rounds of the chip's block slots) x (stages per block + a fixed per-block cost
   // of ~3 stages: position decode, tap masks, partial stores); ties keep the smaller split
   const int64_t base = (int64_t)a.mtiles * a.ptiles * a.ncls;
-  int occ = (int)(163840 / lds_bytes(pl.BM, pl.BP));
+  int occ = (int)(163840 / (pl.split ? split_lds_bytes(pl.BM, pl.BP) : lds_bytes(pl.BM, pl.BP)));
   occ = occ > 4 ? 4 : (occ < 1 ? 1 : occ);
   const int64_t slots = (int64_t)occ * tb::num_cu();
   const int stages = (Kmax + KC - 1) / KC;
@@ -350,10 +423,12 @@ int make_plan(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride,
   return TB_OK;
 }
 
-template <int BM, int BP, int WGM>
+template <int I>
 hipError_t launch(const CGArgs& a, hipStream_t st) {
+  constexpr TileCfg c = kTiles[I];
   const int64_t nb = (int64_t)a.mtiles * a.ptiles * a.nsplit * a.ncls;
-  return launch_tile<&k_conv_gemm<BM, BP, WGM>>(lds_bytes(BM, BP), nb, a, st);
+  return launch_tile<&k_conv_gemm<c.BM, c.BP, c.WGM, c.NT, c.split>, c.NT>(
+      c.split ? split_lds_bytes(c.BM, c.BP) : lds_bytes(c.BM, c.BP), nb, a, st);
 }
 
 }  // namespace
@@ -361,7 +436,7 @@ hipError_t launch(const CGArgs& a, hipStream_t st) {
 size_t tb_conv3d_gemm_workspace_bytes(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride, int ksize) {
   Plan pl;
   if (make_plan(mode, N, Cin, M, D, H, Wd, stride, ksize, pl) != TB_OK) return 0;
-  return 4 * (align_floats(pl.pack_floats) + align_floats(pl.part_floats)) + 256;
+  return pl.ws_bytes();
 }
 
 int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, const float* bias, const float* add,
@@ -372,8 +447,7 @@ int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, co
   const int rc = make_plan(mode, N, Cin, M, D, H, Wd, stride, ksize, pl);
   if (rc != TB_OK) return rc;
   CGArgs& a = pl.a;
-  const size_t need = 4 * (align_floats(pl.pack_floats) + align_floats(pl.part_floats)) + 256;
-  if (!ws || ws_bytes < need) return TB_ERR_WORKSPACE;
+  if (!ws || ws_bytes < pl.ws_bytes()) return TB_ERR_WORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   a.x = x, a.bias = bias, a.add = add, a.y = y;
   a.xsn = xsn > 0 ? xsn : (int64_t)Cin * a.xsc;
@@ -381,17 +455,19 @@ int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, co
   a.addsn = addsn > 0 ? addsn : a.ysn;
   a.xbytes = 4 * ((int64_t)(N - 1) * a.xsn + (int64_t)Cin * a.xsc);
   if (a.xbytes >= (int64_t)1 << 31) return TB_ERR_UNSUPPORTED_SIZE;
-  float* wsf = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+  char* wsb = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
   {
     const int64_t total = (int64_t)pl.pack_floats;
-    hipLaunchKernelGGL(k_cg_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, wsf, mode, total, a);
-    a.A = wsf;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (pl.split) hipLaunchKernelGGL(k_cg_pack<true>, grid, dim3(256), 0, st, W, (void*)wsb, mode, total, a);
+    else hipLaunchKernelGGL(k_cg_pack<false>, grid, dim3(256), 0, st, W, (void*)wsb, mode, total, a);
+    a.A = wsb;
   }
-  a.part = wsf + align_floats(pl.pack_floats);
+  a.part = reinterpret_cast<float*>(wsb + pl.pack_bytes());
   hipError_t e = hipSuccess;
-  if (pl.BM == 32) e = launch<32, 128, 1>(a, st);
-  else if (pl.BM == 64) e = launch<64, 64, 2>(a, st);
-  else e = launch<128, 128, 2>(a, st);
+  if (pl.BM == 32) e = launch<0>(a, st);
+  else if (pl.BM == 64) e = launch<1>(a, st);
+  else e = launch<2>(a, st);
   if (e != hipSuccess) return TB_ERR_HIP;
   if (a.nsplit > 1) {
     const int64_t tot = (int64_t)a.ncls * a.M * a.P;

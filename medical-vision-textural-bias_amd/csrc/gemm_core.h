@@ -1,7 +1,10 @@
 // gemm_core.h -- the tile pipeline shared by the matrix-core conv GEMMs (conv_gemm.hip: forward and
-// input gradient; conv_wgrad_gemm.hip: weight gradient).
+// input gradient; conv_wgrad_gemm.hip: weight gradient), as two tiles with one contract (run / stage /
+// epilogue, what the kernels rely on below): Tile, exact f32 on mfma_f32_32x32x2f32 (the weight gradient
+// and conv_gemm.hip's 32 x 128 and 64 x 64 tiles), and SplitTile, split precision on
+// v_mfma_f32_32x32x16_bf16 (split_bf16.h; conv_gemm.hip's 128 x 128 tile), described at its definition.
 //
-// A 256-thread block computes a BM x BP tile of C = A B^T over stages of KC = 32 reduction elements.  A
+// Tile: a 256-thread block computes a BM x BP tile of C = A B^T over stages of KC = 32 reduction elements.  A
 // stage lives in LDS as BM rows of A then BP rows of B, each [32 k + 4 pad] floats, k in natural order.
 // The four waves (WGM x 4 / WGM) own TM x TN sub-tiles of 32 x 32 on mfma_f32_32x32x2f32 (exact f32: one
 // rounding per product, as a k-ordered fmaf chain); each lane reads its 16 operands of a stage as four
@@ -16,9 +19,9 @@
 //     (offset 0x80000000).
 //   * nst == 0 is a real case (conv_gemm.hip: the k slices of a sub-pixel class past its K): the block
 //     loads nothing, still reaches the barrier, and its epilogue stores zeros.
-//   * The MFMA order along the reduction is fixed -- within a stage step st pairs element st (lanes 0-31)
-//     with element 16 + st (lanes 32-63), half 0 then half 1, stages in order -- so results are
-//     bit-reproducible across changes of everything else.
+//   * The MFMA order along the reduction is fixed -- Tile: within a stage step st pairs element st (lanes
+//     0-31) with element 16 + st (lanes 32-63), half 0 then half 1, stages in order; SplitTile: see there
+//     -- so results are bit-reproducible across changes of everything else.
 //   * Slot and buffer indices are compile-time (Idx<0> / Idx<1>): the stagers' register slots stay in
 //     registers; a runtime index would send them to scratch.
 #pragma once
@@ -28,6 +31,8 @@
 #include <cstdint>
 #include <mutex>
 #include <type_traits>
+
+#include "split_bf16.h"
 
 namespace tb {
 namespace gemm {
@@ -139,9 +144,122 @@ struct Tile {
 
 inline size_t lds_bytes(int BM, int BP) { return (size_t)2 * (BM + BP) * RS * sizeof(float); }
 
-// Launch nb blocks of the tile kernel Kern with `lds` bytes of dynamic LDS; the first launch of each
-// kernel raises its dynamic-LDS limit.
-template <auto Kern, class Args>
+// ---- the split-precision tile --------------------------------------------------------------------------
+constexpr int SRS = 80;  // LDS bytes per row of one part image: 32 k bf16 + 16 B pad
+
+// NT threads (NT / 64 waves as WGM x NT / 64 / WGM) compute the BM x BP tile in split precision
+// (split_bf16.h): the same run / stage / epilogue, the same 32-k stages, the same register slots and
+// barriers as Tile, the stage in LDS as three bf16 part images.
+//
+// LDS, per stage buffer: image p (part p = 0, 1, 2) at p * (BM + BP) * SRS bytes, in it row r (A rows 0 ..
+// BM - 1, then the BP rows of B) at r * SRS, k innermost: element k of a row at byte 2 k.  The stagers write
+// 16-B octets (8 k of one row and part); fragment (row l32, k = 16 ks + 8 kk .. + 7) is one ds_read_b128.
+// Banks, with the row pitch of 20 dwords:
+//   * ds_read_b128 is served in groups of 16 lanes, rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one
+//     kk, 64 banks: 20 r mod 64 = 4 (5 r mod 16); either row set holds one row of every residue mod 16
+//     ({0-3, 12-15, 20-27} = {0-3, 12-15, 4-11} mod 16) and 5 is odd, so 5 r mod 16 takes 16 different
+//     values: the 16 reads of 4 dwords cover the 64 banks once;
+//   * ds_write_b128 is served in groups of 8 consecutive lanes = 8 consecutive rows at one k octet, 32
+//     banks: 20 r mod 32 = 4 (5 r mod 8), eight different values: the 32 banks once.
+//
+// Order along the reduction (fixed, so results are bit-reproducible): stages in order; in a stage the 16-k
+// step ks = 0 (k 0 - 15: lanes 0-31 elements 0-7, lanes 32-63 elements 8-15) then ks = 1; in a step, per
+// sub-tile, a1 b1, a0 b2, a2 b0, a0 b1, a1 b0 into `lo` and a0 b0 into `hi`.  hi + lo is taken once, in the
+// epilogue, before the kernel's sink adds bias / `add` or stores the partial.
+//
+// The accumulator of v_mfma_f32_32x32x16_bf16 maps as that of v_mfma_f32_32x32x2_f32 (CDNA4 ISA, "32x32"
+// output layout, four 8-row blocks: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)); A is
+// row (lane & 31), k = 8 (lane >> 5) + j, B likewise with its column.
+template <int BM, int BP, int WGM, int NT>
+struct SplitTile {
+  static constexpr int NW = NT / 64, WGN = NW / WGM;
+  static constexpr int TM = BM / WGM / 32, TN = BP / WGN / 32;
+  static constexpr int IMG = (BM + BP) * SRS;  // bytes per part image
+  static constexpr int LBUF = 3 * IMG;         // bytes per stage buffer
+  static_assert(TM >= 1 && TN >= 1 && WGM * WGN * 64 == NT, "tile");
+
+  f32x16s hi[TM][TN], lo[TM][TN];
+  int wm, wn, kk, l32;
+
+  __device__ __forceinline__ SplitTile(int w, int lane) : wm(w % WGM), wn(w / WGM), kk(lane >> 5), l32(lane & 31) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hi[tm][tn][r] = 0.f, lo[tm][tn][r] = 0.f;
+  }
+
+  // byte offset in a part image of A row `row` / B row `row`, k octet `oct` (the stagers' store address)
+  static __device__ __forceinline__ int a_off(int row, int oct) { return row * SRS + 16 * oct; }
+  static __device__ __forceinline__ int b_off(int row, int oct) { return (BM + row) * SRS + 16 * oct; }
+
+  // the 16-k step ks of the stage in LDS buffer sl
+  template <int sl, int ks>
+  __device__ __forceinline__ void half(const char* lds) {
+    const char* L = lds + sl * LBUF + 32 * ks + 16 * kk;
+    bf16x8 af[TM][3], bf[TN][3];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        af[tm][p] = *reinterpret_cast<const bf16x8*>(L + p * IMG + ((wm * TM + tm) * 32 + l32) * SRS);
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        bf[tn][p] = *reinterpret_cast<const bf16x8*>(L + p * IMG + (BM + (wn * TN + tn) * 32 + l32) * SRS);
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) mfma_split6_32(af[tm], bf[tn], hi[tm][tn], lo[tm][tn]);
+  }
+
+  template <class Load, class Store>
+  __device__ __forceinline__ void run(const char* lds, int nst, Load&& load, Store&& store) {
+    if (nst > 0) {
+      load(Idx<0>{}, 0);
+      store(Idx<0>{});
+      load(Idx<1>{}, 1);
+    }
+    __syncthreads();
+    for (int s = 0; s < nst; s += 2) {
+      stage<0>(lds, s, load, store);
+      if (s + 1 < nst) stage<1>(lds, s + 1, load, store);
+    }
+  }
+
+  // stage s: its first 16 k, then the loads of stage s + 2, the last 16 k, stage s + 1 (split at this
+  // store) to the other LDS buffer
+  template <int sl, class Load, class Store>
+  __device__ __forceinline__ void stage(const char* lds, int s, Load& load, Store& store) {
+    half<sl, 0>(lds);
+    load(Idx<sl>{}, s + 2);
+    half<sl, 1>(lds);
+    store(Idx<1 - sl>{});
+    __syncthreads();
+  }
+
+  // as Tile::epilogue, on hi + lo
+  template <class Column>
+  __device__ __forceinline__ void epilogue(Column&& column) {
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+      auto sink = column((wn * TN + tn) * 32 + l32);
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          sink((wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk, hi[tm][tn][r] + lo[tm][tn][r]);
+    }
+  }
+};
+
+inline size_t split_lds_bytes(int BM, int BP) { return (size_t)2 * 3 * (BM + BP) * SRS; }
+
+// Launch nb blocks of NT threads of the tile kernel Kern with `lds` bytes of dynamic LDS; the first launch
+// of each kernel raises its dynamic-LDS limit.
+template <auto Kern, int NT = NTH, class Args>
 hipError_t launch_tile(size_t lds, int64_t nb, const Args& a, hipStream_t st) {
   static std::once_flag once;
   static hipError_t attr = hipSuccess;
@@ -149,7 +267,7 @@ hipError_t launch_tile(size_t lds, int64_t nb, const Args& a, hipStream_t st) {
     attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(Kern, dim3((unsigned)nb), dim3(NTH), lds, st, a);
+  hipLaunchKernelGGL(Kern, dim3((unsigned)nb), dim3(NT), lds, st, a);
   return hipGetLastError();
 }
 

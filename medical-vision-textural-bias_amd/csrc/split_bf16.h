@@ -71,4 +71,17 @@ __device__ __forceinline__ void mfma_split6(const bf16x8 (&a)[3], const bf16x8 (
   hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], hi, 0, 0, 0);
 }
 
+// The same step on v_mfma_f32_32x32x16_bf16 (16 k, a 32 x 32 result: 6 x 32 cycles where the sixteen
+// mfma_f32_32x32x2f32 of 32 k take 1024, and half the LDS bytes per FLOP of the 16 x 16 form), same order.
+typedef float f32x16s __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ void mfma_split6_32(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16s& hi, f32x16s& lo) {
+  lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], lo, 0, 0, 0);
+  lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], lo, 0, 0, 0);
+  lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], lo, 0, 0, 0);
+  lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], lo, 0, 0, 0);
+  lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], lo, 0, 0, 0);
+  hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], hi, 0, 0, 0);
+}
+
 }  // namespace tb
