@@ -289,6 +289,17 @@ int tb_conv3d_wgrad_config(int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
                            int64_t* cfg);
 
 /*
+ * The launch tb_conv3d_wgrad_ws_f32 makes for these sizes with 16-byte aligned G and X and a workspace of
+ * tb_conv3d_wgrad_ws_bytes, without launching anything (host only): cfg[0] = kind (0: the general split-K
+ * kernel of tb_conv3d_wgrad_config; z-marching routes 1: >= 8 channels stride 1, 2: >= 8 channels stride 2,
+ * 3: few channels stride 1, 4: few input channels stride 2), cfg[1] = YB (output rows per workgroup),
+ * cfg[2] = zlen (planes per z segment) and cfg[3] = ZS (z segments; both 0 for kind 0), cfg[4], cfg[5] =
+ * grid x, y, cfg[6] = LDS bytes per workgroup, cfg[7] = workspace bytes (0 for kind 0).  Same error codes.
+ */
+int tb_conv3d_wgrad_plan(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad,
+                         int64_t* cfg);
+
+/*
  * Dice statistics of DiceLoss(sigmoid, squared_pred) (MONAI 0.5 formula, used by the reference's
  * train step stylized_gibbs12p5.py:201): for NC instances of S contiguous voxels of logits x and
  * target t, sums[nc] = {sum t p, sum t^2 (t), sum p^2 (p)} in float64 (DEVICE double[NC][3],
@@ -574,7 +585,7 @@ int tb_set_compiled_plans(int enable);
  * Channel-volumes per pass A -> B -> C chain inside tb_kspace_filter_f32.  n > 0 runs the three
  * passes per chunk of n channel-volumes (the chunk's half spectrum is re-read by B and C from the
  * 256 MiB Infinity Cache rather than HBM), n = 0 runs each pass once over the whole batch group,
- * n < 0 restores the default (TEXBIAS_CHUNK_BC, else 0; chunking measured slower at C3).  Results
+ * n < 0 restores the default (0: chunking measured slower at C3).  Results
  * do not depend on n (bit-identical).
  */
 int tb_set_chain_chunk(int n);

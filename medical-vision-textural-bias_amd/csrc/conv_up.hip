@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "num_cu.h"
+#include "conv_host.h"
 #include "split_bf16.h"
 #include "texbias.h"
 
@@ -350,31 +350,16 @@ __global__ __launch_bounds__(NTH) void k_convT_fewout(TArgs a) {
   }
 }
 
-// z segment length for `base` blocks per z segment, `per_cu` blocks resident per CU: rounds x (len + fill)
-int zseg(int D, int base, int per_cu, int fill) {
-  const int slots = per_cu * tb::num_cu();
-  int best = 1 << 30, zl = D;
-  for (int l = D; l >= 1; --l) {
-    const int zs = (D + l - 1) / l, rounds = (base * zs + slots - 1) / slots, cost = rounds * (l + fill);
-    if (cost < best) best = cost, zl = l;
-  }
-  return zl;
-}
-
 template <int CIN, int MOUT, int WV>
 int launch_s2(S2Args& a, size_t lds, int N, hipStream_t st) {
   constexpr int TY = 3;
   // CIN = 4, MOUT = 32 (the stacked entry unit + residual): 512 threads splitting the output pairs
   constexpr int NT = (CIN == 4 && MOUT == 32) ? 512 : 256;
-  auto kern = k_conv_s2_fewin<CIN, MOUT, TY, WV, NT>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
   const int per_cu = lds <= 81920 ? 2 : 1;
-  a.zlen = zseg(a.Do, N * a.nyb, per_cu, 1);
+  a.zlen = tb::zseg(a.Do, N * a.nyb, per_cu, 1);
   a.ZS = (a.Do + a.zlen - 1) / a.zlen;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(NT), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(k_conv_s2_fewin<CIN, MOUT, TY, WV, NT>, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(NT), lds, st,
+                        a);
 }
 
 }  // namespace
@@ -426,7 +411,7 @@ int tb_convT3d_fewout_f32(const float* x, const float* W, const float* bias, flo
   const size_t lds = (size_t)4 * 2 * Cin * a.CS;
   if (lds > 163840) return TB_ERR_UNSUPPORTED_SIZE;
   const int per_cu = lds <= 81920 ? 2 : 1;
-  a.zlen = zseg(Di, N * a.nyb, per_cu, 1);
+  a.zlen = tb::zseg(Di, N * a.nyb, per_cu, 1);
   a.ZS = (Di + a.zlen - 1) / a.zlen;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(N * a.nyb * a.ZS));
@@ -436,21 +421,13 @@ int tb_convT3d_fewout_f32(const float* x, const float* W, const float* bias, flo
   TB_T(1, 1) TB_T(1, 2) TB_T(1, 3) TB_T(2, 1) TB_T(2, 2) TB_T(2, 3) TB_T(3, 1) TB_T(3, 2) TB_T(3, 3) TB_T(4, 1)
   TB_T(4, 2) TB_T(4, 3)
 #undef TB_T
-  // (channels per FMA-loop iteration of the 512-thread form: 1 / 2 / 4 = 296 / 294 / 311 us for the C3
-  // 32 -> 3 layer: one)
-  constexpr int U = 1;
-  if (big && Mout == 3)
-    kern = U == 4 ? k_convT_fewout<3, 6, 20, 512, 4> : U == 2 ? k_convT_fewout<3, 6, 20, 512, 2>
-                                                      : k_convT_fewout<3, 6, 20, 512>;
-  else if (big)
+  // (the 512-thread form takes one input channel per FMA-loop iteration: 1 / 2 / 4 measured 296 / 294 / 311 us
+  // for the C3 32 -> 3 layer)
+  if (big)
     kern = Mout == 1 ? k_convT_fewout<1, 6, 20, 512> : Mout == 2 ? k_convT_fewout<2, 6, 20, 512>
-                                                     : k_convT_fewout<4, 6, 20, 512>;
+         : Mout == 3 ? k_convT_fewout<3, 6, 20, 512> : k_convT_fewout<4, 6, 20, 512>;
   if (!kern) return TB_ERR_UNSUPPORTED_SIZE;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, grid, dim3(nth), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, grid, dim3(nth), lds, st, a);
 }
 
 // ------------------------------------------------- stride-1 3x3x3 conv, 16 -> 16 channels, on MFMA
@@ -938,7 +915,7 @@ static int split16_call(const float* x, const float* W, const float* bias, const
   a.nyb = (H + 2) / 3;
   const int NS = 4 * x16_slot(Wd) <= 163840 ? 4 : 3;  // 4-slot plane ring where it fits (W <= 80)
   const size_t lds = NS * x16_slot(Wd);
-  a.zlen = zseg(D, N * a.nyb, 1, 2);  // 8 waves at 2 per SIMD: one block per CU
+  a.zlen = tb::zseg(D, N * a.nyb, 1, 2);  // 8 waves at 2 per SIMD: one block per CU
   a.ZS = (D + a.zlen - 1) / a.zlen;
   void (*kern)(X16Args) = nullptr;
 #define TB_X16(NX, S) \
@@ -949,16 +926,12 @@ static int split16_call(const float* x, const float* W, const float* bias, const
   }
 #undef TB_X16
   if (NS != (Wd <= 80 ? 4 : 3)) return TB_ERR_UNSUPPORTED_SIZE;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
   // persistent shares when the (n, yb, z segment) grid leaves CUs idle, as for k_conv3d_fwd16
   a.ncol = N * a.nyb;
   unsigned nblk = (unsigned)(N * a.nyb * a.ZS);
   a.persist = (int64_t)a.ncol * D >= 8LL * tb::num_cu() && nblk % tb::num_cu() != 0;
   if (a.persist) nblk = (unsigned)tb::num_cu();
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, reinterpret_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, dim3(nblk), dim3(512), lds, reinterpret_cast<hipStream_t>(stream), a);
 }
 
 static int fwd16_call(const float* x, const float* W, const float* bias, const float* add, float* y, int N, int D, int H,
@@ -984,49 +957,32 @@ static int fwd16_call(const float* x, const float* W, const float* bias, const f
   const size_t lds = (size_t)NS * 4 * 16 * a.RX;
   if (lds > 163840) return TB_ERR_UNSUPPORTED_SIZE;
   const int per_cu = 163840 / (int)lds >= 2 ? 2 : 1;
-  a.zlen = zseg(D, N * a.nyb, per_cu, 2);
+  a.zlen = tb::zseg(D, N * a.nyb, per_cu, 2);
   a.ZS = (D + a.zlen - 1) / a.zlen;
   void (*kern)(F16Args) = nullptr;
   // 512 threads per block: 8 waves, 2 per SIMD sharing the matrix core, hide the B-fragment LDS reads the
-  // compiler issues only 1-3 ahead (YB = 3: 421 -> 365 us per C3 call against 256 threads)
-  constexpr int NTv = 512;
-  // the B fragments read a tap ahead of their MFMAs, interleaved one LDS read per MFMA (sched_group_barrier)
-  // and a 4-slot plane ring, one barrier per step (C3, by scripts/diag/conv_kern_bench.py: forward
-  // 385 -> 374 us, input gradient 361 -> 353 us against the earlier form, still the fallback below)
-  constexpr bool PFv = true;
-  if (PFv && YB == 3 && NTv == 512 && Wd == 80) {
-    kern = add ? (NS == 4 ? k_conv3d_fwd16<3, 5, 512, true, true, 4> : k_conv3d_fwd16<3, 5, 512, true, true, 3>)
-               : (NS == 4 ? k_conv3d_fwd16<3, 5, 512, false, true, 4> : k_conv3d_fwd16<3, 5, 512, false, true, 3>);
-  } else
-#define TB_F16C(Y, X, T) \
-  kern = add ? (NS == 4 ? k_conv3d_fwd16<Y, X, T, true, false, 4> : k_conv3d_fwd16<Y, X, T, true, false, 3>) \
-             : (NS == 4 ? k_conv3d_fwd16<Y, X, T, false, false, 4> : k_conv3d_fwd16<Y, X, T, false, false, 3>);
-#define TB_F16(Y, T)                                                                                   \
-  if (YB == Y && NTv == T) switch (Wd / 16) {                                                          \
-      case 1: TB_F16C(Y, 1, T) break;                                                                  \
-      case 2: TB_F16C(Y, 2, T) break;                                                                  \
-      case 3: TB_F16C(Y, 3, T) break;                                                                  \
-      case 4: TB_F16C(Y, 4, T) break;                                                                  \
-      case 5: TB_F16C(Y, 5, T) break;                                                                  \
-      case 6: TB_F16C(Y, 6, T) break;                                                                  \
-      case 7: TB_F16C(Y, 7, T) break;                                                                  \
-      case 8: TB_F16C(Y, 8, T) break;                                                                  \
-      default: return TB_ERR_UNSUPPORTED_SIZE;                                                         \
-    }
-  TB_F16(3, 512)
+  // compiler issues only 1-3 ahead (YB = 3: 421 -> 365 us per C3 call against 256 threads).
+  // W = 80 takes the PF form: the B fragments read a tap ahead of their MFMAs, interleaved one LDS read per
+  // MFMA (sched_group_barrier) and a 4-slot plane ring, one barrier per step (C3, by
+  // scripts/diag/conv_kern_bench.py: forward 385 -> 374 us, input gradient 361 -> 353 us against the earlier
+  // form, which the other widths keep)
+#define TB_F16(X, PF)                                                                                             \
+  case X:                                                                                                         \
+    kern = add ? (NS == 4 ? k_conv3d_fwd16<YB, X, 512, true, PF, 4> : k_conv3d_fwd16<YB, X, 512, true, PF, 3>)     \
+               : (NS == 4 ? k_conv3d_fwd16<YB, X, 512, false, PF, 4> : k_conv3d_fwd16<YB, X, 512, false, PF, 3>);  \
+    break;
+  switch (Wd / 16) {
+    TB_F16(1, false) TB_F16(2, false) TB_F16(3, false) TB_F16(4, false) TB_F16(5, true) TB_F16(6, false)
+    TB_F16(7, false) TB_F16(8, false)
+    default: return TB_ERR_UNSUPPORTED_SIZE;
+  }
 #undef TB_F16
-#undef TB_F16C
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
   // persistent shares when the (n, yb, z segment) grid leaves CUs idle (C3: 240 blocks of 256)
-  constexpr int persist_env = 1;
   a.ncol = N * a.nyb;
   unsigned nblk = (unsigned)(N * a.nyb * a.ZS);
-  a.persist = persist_env && per_cu == 1 && (int64_t)a.ncol * D >= 8LL * tb::num_cu() && nblk % tb::num_cu() != 0;
+  a.persist = per_cu == 1 && (int64_t)a.ncol * D >= 8LL * tb::num_cu() && nblk % tb::num_cu() != 0;
   if (a.persist) nblk = (unsigned)tb::num_cu();
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(NTv), lds, reinterpret_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, dim3(nblk), dim3(512), lds, reinterpret_cast<hipStream_t>(stream), a);
 }
 
 // ------------------------------------------------- ConvTranspose3d(64 -> 16, 3, s2, p1, op1) on MFMA
@@ -1214,7 +1170,7 @@ int tb_convT3d_mfma_f32(const float* x, const float* W, const float* bias, float
   a.nyb = (Hi + YB - 1) / YB;
   const size_t lds = (size_t)4 * (2 * Cin * a.RX + 2 * 4 * 8 * 256);
   if (lds > 163840) return TB_ERR_UNSUPPORTED_SIZE;
-  a.zlen = zseg(Di, N * a.nyb, 1, 1);
+  a.zlen = tb::zseg(Di, N * a.nyb, 1, 1);
   a.ZS = (Di + a.zlen - 1) / a.zlen;
   const int nl = (Cin * (YB + 1) * (Wi / 4) + 255) / 256;
   void (*kern)(T64Args) = nullptr;
@@ -1225,11 +1181,8 @@ int tb_convT3d_mfma_f32(const float* x, const float* W, const float* bias, float
 #undef TB_NL
     default: return TB_ERR_UNSUPPORTED_SIZE;
   }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(256), lds,
+                        reinterpret_cast<hipStream_t>(stream), a);
 }
 
 // ------------------------------------------------- stride-1 3x3x3 conv, C -> C channels (C = 32, 64), on MFMA
@@ -1445,8 +1398,7 @@ static int mfma_call(const float* x, const float* W, const float* bias, const fl
   // slower here, 245 vs 211 us at 32 -> 32, unlike k_conv3d_fwd16).  (Persistent step
   // shares as in k_conv3d_fwd16 measured no gain at 32 -> 32, 186 vs 184 us, and the loop they need cost
   // the 64 -> 64 kernel 107 -> 144 us: not used.)
-  constexpr int NTv = 256;  // only the measured best (256 threads) is instantiated
-  const int NC = NTv == 512 ? 3 : 5;
+  constexpr int NC = 5;
   const int G = C / 16;
   S1Args a{};
   a.x = x, a.W = W, a.bias = bias, a.add = add, a.y = y, a.D = D, a.H = H, a.Wd = Wd;
@@ -1456,19 +1408,19 @@ static int mfma_call(const float* x, const float* W, const float* bias, const fl
   a.MG = G == 2 ? 1 : 4;  // 32: both output tiles in the block; 64: one tile per block, 4 block groups
   size_t lds = 0;
   // rows per step: the most whose positions fit one round of the block's NWG x NC position tiles
-  int YB = std::max(1, 16 * NC * (NTv / 256) / Wd);
+  int YB = std::max(1, 16 * NC / Wd);
   for (; YB >= 1; --YB) {
     a.RX = (YB + 2) * a.PX;
     while ((a.RX & 31) != 16) ++a.RX;
-    lds = (size_t)4 * (3 * C * a.RX + (NTv / 64) * NC * 256 + 64);
+    lds = (size_t)4 * (3 * C * a.RX + 4 * NC * 256 + 64);  // 4 waves
     if (lds <= 163840) break;
   }
   if (YB < 1) return TB_ERR_UNSUPPORTED_SIZE;
   a.YB = YB > H ? H : YB;
   a.nyb = (H + a.YB - 1) / a.YB;
-  a.zlen = zseg(D, N * a.nyb * a.MG, 1, 2);
+  a.zlen = tb::zseg(D, N * a.nyb * a.MG, 1, 2);
   a.ZS = (D + a.zlen - 1) / a.zlen;
-  const int nl = (C * (a.YB + 2) * (Wd / 4) + NTv - 1) / NTv;
+  const int nl = (C * (a.YB + 2) * (Wd / 4) + 255) / 256;
   void (*kern)(S1Args) = nullptr;
 #define TB_NL(k)                                                                                      \
   case k:                                                                                             \
@@ -1480,10 +1432,6 @@ static int mfma_call(const float* x, const float* W, const float* bias, const fl
     default: return TB_ERR_UNSUPPORTED_SIZE;
   }
 #undef TB_NL
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) !=
-      hipSuccess)
-    return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(N * a.nyb * a.MG * a.ZS)), dim3(NTv), lds,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, dim3((unsigned)(N * a.nyb * a.MG * a.ZS)), dim3(256), lds,
+                        reinterpret_cast<hipStream_t>(stream), a);
 }

@@ -25,7 +25,7 @@
 
 #include <cstdlib>
 
-#include "num_cu.h"
+#include "conv_host.h"
 #include "texbias.h"
 
 namespace {
@@ -1178,29 +1178,29 @@ int pad_mod32(int v, int rem) {
   return v;
 }
 
-template <int S, int TX, int SEG>
-int launch(const WgArgs& a, int blocks_y, size_t lds, hipStream_t st) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3d_wgrad<S, TX, SEG>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  // two blocks per CU over the whole chip, never more chunks than exist
-  constexpr int target = 512;
-  int64_t gx = (target + blocks_y - 1) / blocks_y;
+// grid.x of the general kernels: 512 blocks (two per CU over the whole chip) over the `by` channel tiles,
+// 1024 for k_conv3d_wgrad_mz (TX = 9); never more chunks than exist
+unsigned wg_grid_x(const WgArgs& a, int TX, int by) {
+  int64_t gx = TX == 9 ? 1024 : (512 + by - 1) / by;
   if (gx > a.nchunks) gx = a.nchunks;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((k_conv3d_wgrad<S, TX, SEG>), dim3((unsigned)gx, (unsigned)blocks_y), dim3(NT), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return gx < 1 ? 1u : (unsigned)gx;
 }
 
-template <int S, int TX>
-int launch_seg(const WgArgs& a, int seg, int by, size_t lds, hipStream_t st) {
+// k_conv3d_wgrad<stride, TX, SEG> or, for TX = 9, k_conv3d_wgrad_mz<SEG>
+int launch_wg(const WgArgs& a, int stride, int TX, int seg, int by, size_t lds, hipStream_t st) {
+  void (*kern)(WgArgs) = nullptr;
+#define TB_WG(SEG)                                                                                             \
+  case SEG:                                                                                                    \
+    kern = TX == 9 ? k_conv3d_wgrad_mz<SEG>                                                                    \
+                   : stride == 1 ? (TX == 1 ? k_conv3d_wgrad<1, 1, SEG> : k_conv3d_wgrad<1, 3, SEG>)            \
+                                 : (TX == 1 ? k_conv3d_wgrad<2, 1, SEG> : k_conv3d_wgrad<2, 3, SEG>);            \
+    break;
   switch (seg) {
-    case 1: return launch<S, TX, 1>(a, by, lds, st);
-    case 2: return launch<S, TX, 2>(a, by, lds, st);
-    case 3: return launch<S, TX, 3>(a, by, lds, st);
-    case 4: return launch<S, TX, 4>(a, by, lds, st);
+    TB_WG(1) TB_WG(2) TB_WG(3) TB_WG(4)
     default: return TB_ERR_UNSUPPORTED_SIZE;
   }
+#undef TB_WG
+  return tb::launch_lds(kern, dim3(wg_grid_x(a, TX, by), (unsigned)by), dim3(NT), lds, st, a);
 }
 
 // Tiling of one weight-gradient call: TX (taps vs (c, tx) columns), SEG (64-wide row segments a
@@ -1236,23 +1236,7 @@ int wg_setup_mz(WgArgs& a, int& seg, int& by, size_t& lds, int N, int M, int Cc,
   return TB_OK;
 }
 
-template <int SEG>
-int launch_mz(const WgArgs& a, size_t lds, hipStream_t st) {
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3d_wgrad_mz<SEG>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  constexpr int target = 1024;
-  int64_t gx = target;
-  if (gx > a.nchunks) gx = a.nchunks;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(k_conv3d_wgrad_mz<SEG>, dim3((unsigned)gx), dim3(NT), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
-}
-
-bool use_mz(int M, int Cc, int stride) {
-  constexpr bool on = true;
-  return on && stride == 1 && M <= 5 && Cc <= 5;
-}
+bool use_mz(int M, int Cc, int stride) { return stride == 1 && M <= 5 && Cc <= 5; }
 
 int wg_setup(WgArgs& a, int& seg, int& TX, int& by, size_t& lds, int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
              int Hi, int Wi, int stride, int pad) {
@@ -1297,13 +1281,12 @@ int wg_setup(WgArgs& a, int& seg, int& TX, int& by, size_t& lds, int N, int M, i
 
 // z-marching stride-1 kernel (k_conv3d_wgrad_zm): 16-channel tiles, W % 4 == 0 (16-B rows), W <= 80,
 // at least 8 output and 8 input channels (the few-channel layers keep their own tilings)
-bool use_zm(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi, const void* G, const void* X) {
-  constexpr bool on = true;
-  return on && stride == 1 && M >= 8 && Cc >= 8 && Do == Di && Ho == Hi && Wo == Wi && Wo % 4 == 0 && Wo <= 80 &&
-         (reinterpret_cast<uintptr_t>(G) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+// (every z-marching route also needs 16-byte aligned G and X: zroute)
+bool use_zm(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi) {
+  return stride == 1 && M >= 8 && Cc >= 8 && Do == Di && Ho == Hi && Wo == Wi && Wo % 4 == 0 && Wo <= 80;
 }
 
-int zm_setup(ZmArgs& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, int H, int W, int ncu) {
+int zm_setup(ZmArgs& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, int H, int W) {
   a.N = N; a.M = M; a.Cc = Cc; a.D = D; a.H = H; a.W = W;
   a.W4 = W;  // W % 4 == 0
   a.PX = ((W + 3 + 1) / 2) * 2;  // cols 0..W + 2 (data at 2..W + 1), even (8-B stores)
@@ -1322,22 +1305,8 @@ int zm_setup(ZmArgs& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, in
   a.nyb = (H + a.YB - 1) / a.YB;
   a.mtiles = (M + 15) / 16;
   a.ctiles = (Cc + 15) / 16;
-  // z segments: the launch takes ceil(blocks / (CUs x blocks per CU)) rounds of zlen + 2 plane steps
-  // (two ring-fill planes per segment): the segment length minimising that
-  const int per_cu = 1;
-  const int base = N * a.nyb * a.mtiles * a.ctiles;
-  int best = 1 << 30;
-  a.zlen = D;
-  for (int zl = D; zl >= 4 || zl == D; --zl) {
-    const int zs = (D + zl - 1) / zl;
-    const int rounds = (base * zs + ncu * per_cu - 1) / (ncu * per_cu);
-    const int cost = rounds * (zl + 2);
-    if (cost < best) {
-      best = cost;
-      a.zlen = zl;
-    }
-    if (zl <= 1) break;
-  }
+  // z segments (one block per CU, two ring-fill planes per segment), not shorter than 4 unless that is all of D
+  a.zlen = tb::zseg(D, N * a.nyb * a.mtiles * a.ctiles, 1, 2, 4);
   a.ZS = (D + a.zlen - 1) / a.zlen;
   grid = dim3((unsigned)(N * a.nyb * a.ZS), (unsigned)(a.mtiles * a.ctiles));
   return TB_OK;
@@ -1348,29 +1317,22 @@ int zm_setup(ZmArgs& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, in
 int launch_zm(const ZmArgs& a, size_t lds, dim3 grid, hipStream_t st) {
   auto kern = a.W > 40 ? (a.YB == 4 ? k_conv3d_wgrad_zm<4, 20, 8> : k_conv3d_wgrad_zm<2, 20, 8>)
                        : (a.YB == 4 ? k_conv3d_wgrad_zm<4, 10, 8> : k_conv3d_wgrad_zm<2, 10, 8>);
-  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, grid, dim3(512), lds, st, a);
 }
 
 // stride-2 z-marching kernel (k_conv3d_wgrad_zm2): >= 8 input channels, Wo % 4 == 0, Wo <= 40,
 // input rows of exactly 2 Wo (padding 1)
-bool use_zm2(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi, const void* G, const void* X) {
-  constexpr bool on = true;
-  return on && stride == 2 && M >= 8 && Cc >= 8 && Wo % 4 == 0 && Wo <= 40 && Wi == 2 * Wo && Hi == 2 * Ho &&
-         Di == 2 * Do && (reinterpret_cast<uintptr_t>(G) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+bool use_zm2(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi) {
+  return stride == 2 && M >= 8 && Cc >= 8 && Wo % 4 == 0 && Wo <= 40 && Wi == 2 * Wo && Hi == 2 * Ho && Di == 2 * Do;
 }
 
 int zm2_setup(Zm2Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi,
-              int Wi, int ncu) {
+              int Wi) {
   a.N = N; a.M = M; a.Cc = Cc; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
   a.PX = ((2 * Wo + 3 + 1) / 2) * 2;
-  constexpr int yb_env = 0;  // rows per block: the first tiling that fits (below)
   a.YB = 0;
   for (int yb : {2, 1}) {  // two output rows per block where the ring fits: twice the MFMAs per staged plane
-    if ((yb_env && yb != yb_env) || yb > Ho) continue;
+    if (yb > Ho) continue;
     for (int rem : {2, 4}) {  // X channel pitch mod 32: 2 (2-way B conflicts), 4 (tighter pad)
       const int rx = pad_mod32((2 * yb + 1) * a.PX, rem), ms = pad_mod32(yb * Wo, 2);
       const size_t ring = (size_t)4 * (2 * 32 * ms + 5 * 16 * rx), red = (size_t)4 * 2 * 27 * 4 * 64;
@@ -1387,19 +1349,8 @@ int zm2_setup(Zm2Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int Do,
   a.nyb = (Ho + a.YB - 1) / a.YB;
   a.mtiles = (M + 31) / 32;
   a.ctiles = (Cc + 15) / 16;
-  const int base = N * a.nyb * a.mtiles * a.ctiles;
-  const int per_cu = 1;  // 8-wave blocks: two waves per SIMD already
-  int best = 1 << 30;
-  a.zlen = Do;
-  for (int zl = Do; zl >= 1; --zl) {
-    const int zs = (Do + zl - 1) / zl;
-    const int rounds = (base * zs + per_cu * ncu - 1) / (per_cu * ncu);
-    const int cost = rounds * (zl + 1);
-    if (cost < best) {
-      best = cost;
-      a.zlen = zl;
-    }
-  }
+  // one block per CU (8-wave blocks: two waves per SIMD already), one ring-fill plane per segment
+  a.zlen = tb::zseg(Do, N * a.nyb * a.mtiles * a.ctiles, 1, 1);
   a.ZS = (Do + a.zlen - 1) / a.zlen;
   grid = dim3((unsigned)(N * a.nyb * a.ZS), (unsigned)(a.mtiles * a.ctiles));
   return TB_OK;
@@ -1408,22 +1359,16 @@ int zm2_setup(Zm2Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int Do,
 int launch_zm2(const Zm2Args& a, size_t lds, dim3 grid, hipStream_t st) {
   auto kern = a.YB == 2 ? (a.Wo <= 20 ? k_conv3d_wgrad_zm2<2, 5, 8> : k_conv3d_wgrad_zm2<2, 10, 8>)
                         : (a.Wo <= 20 ? k_conv3d_wgrad_zm2<1, 5, 8> : k_conv3d_wgrad_zm2<1, 10, 8>);
-  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+  return tb::launch_lds(kern, grid, dim3(512), lds, st, a);
 }
 
 // few-channel stride-2 kernel (k_conv3d_wgrad_zf2): Cc <= 5, Wo % 4 == 0, Wo <= 80, 2x input rows
-bool use_zf2(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi, const void* G, const void* X) {
-  constexpr bool on = true;
-  return on && stride == 2 && Cc <= 5 && Wo % 4 == 0 && Wo <= 80 && Wi == 2 * Wo && Hi == 2 * Ho && Di == 2 * Do &&
-         (reinterpret_cast<uintptr_t>(G) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+bool use_zf2(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi) {
+  return stride == 2 && Cc <= 5 && Wo % 4 == 0 && Wo <= 80 && Wi == 2 * Wo && Hi == 2 * Ho && Di == 2 * Do;
 }
 
 int zf2_setup(Zf2Args& a, int& MT, size_t& lds, dim3& grid, int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
-              int Hi, int Wi, int ncu) {
+              int Hi, int Wi) {
   a.N = N; a.M = M; a.Cc = Cc; a.Do = Do; a.Ho = Ho; a.Wo = Wo; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
   MT = M > 16 ? 2 : 1;
   a.PX = ((2 * Wo + 3 + 1) / 2) * 2;
@@ -1441,47 +1386,29 @@ int zf2_setup(Zf2Args& a, int& MT, size_t& lds, dim3& grid, int N, int M, int Cc
   if (!a.YB) return TB_ERR_UNSUPPORTED_SIZE;
   a.nyb = (Ho + a.YB - 1) / a.YB;
   a.mtiles = (M + 16 * MT - 1) / (16 * MT);
-  const int base = N * a.nyb * a.mtiles;
-  int best = 1 << 30;
-  a.zlen = Do;
-  for (int zl = Do; zl >= 1; --zl) {
-    const int zs = (Do + zl - 1) / zl;
-    const int rounds = (base * zs + ncu - 1) / ncu;
-    const int cost = rounds * (zl + 1);
-    if (cost < best) {
-      best = cost;
-      a.zlen = zl;
-    }
-  }
+  a.zlen = tb::zseg(Do, N * a.nyb * a.mtiles, 1, 1);  // one block per CU, one ring-fill plane per segment
   a.ZS = (Do + a.zlen - 1) / a.zlen;
   grid = dim3((unsigned)(N * a.nyb * a.ZS), (unsigned)a.mtiles);
   return TB_OK;
 }
 
 template <int YB, int MT>
-int launch_zf2_t(const Zf2Args& a, size_t lds, dim3 grid, hipStream_t st) {
-  auto kern = a.Wo <= 40 ? k_conv3d_wgrad_zf2<YB, MT, 10, 8> : k_conv3d_wgrad_zf2<YB, MT, 20, 8>;
-  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+auto zf2_kern(int Wo) {
+  return Wo <= 40 ? k_conv3d_wgrad_zf2<YB, MT, 10, 8> : k_conv3d_wgrad_zf2<YB, MT, 20, 8>;
 }
 int launch_zf2(const Zf2Args& a, int MT, size_t lds, dim3 grid, hipStream_t st) {
-  if (MT == 1) return a.YB == 4 ? launch_zf2_t<4, 1>(a, lds, grid, st) : a.YB == 2 ? launch_zf2_t<2, 1>(a, lds, grid, st) : launch_zf2_t<1, 1>(a, lds, grid, st);
-  return a.YB == 4 ? launch_zf2_t<4, 2>(a, lds, grid, st) : a.YB == 2 ? launch_zf2_t<2, 2>(a, lds, grid, st) : launch_zf2_t<1, 2>(a, lds, grid, st);
+  auto kern = MT == 1 ? (a.YB == 4 ? zf2_kern<4, 1>(a.Wo) : a.YB == 2 ? zf2_kern<2, 1>(a.Wo) : zf2_kern<1, 1>(a.Wo))
+                      : (a.YB == 4 ? zf2_kern<4, 2>(a.Wo) : a.YB == 2 ? zf2_kern<2, 2>(a.Wo) : zf2_kern<1, 2>(a.Wo));
+  return tb::launch_lds(kern, grid, dim3(512), lds, st, a);
 }
 
 // few-channel stride-1 z-marching kernel (k_conv3d_wgrad_zf1): 9 M <= 32, 3 Cc <= 16, W % 4 == 0
-bool use_zf1(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi, const void* G, const void* X) {
-  constexpr bool on = true;
-  return on && stride == 1 && M <= 3 && Cc <= 5 && Do == Di && Ho == Hi && Wo == Wi && Wo % 4 == 0 && Wo <= 256 &&
-         (reinterpret_cast<uintptr_t>(G) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+bool use_zf1(int M, int Cc, int stride, int Do, int Ho, int Wo, int Di, int Hi, int Wi) {
+  return stride == 1 && M <= 3 && Cc <= 5 && Do == Di && Ho == Hi && Wo == Wi && Wo % 4 == 0 && Wo <= 256;
 }
 
-int zf1_setup(Zf1Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, int H, int W, int ncu) {
+int zf1_setup(Zf1Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, int H, int W) {
   a.N = N; a.M = M; a.Cc = Cc; a.D = D; a.H = H; a.W = W;
-  constexpr int yb_env = 0;  // rows per block: the first tiling that fits (below)
   // rows hold whole 16-column groups (zeros past W).  G pitches for the 16-byte A reads, whose banks are
   // taken mod 64 in four 16-lane groups: with row, channel and slot pitches = 40, 24, 56 (mod 64) the 16
   // rows (m, tz, ty) of a tile are at most 2-way on a 16-byte slot for every ring phase (1.75 cycles per
@@ -1491,8 +1418,7 @@ int zf1_setup(Zf1Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, 
   a.GR = pad_mod(Wp, 64, 40);
   a.XR = pad_mod32(Wp + 8, 4);
   a.YB = 0;
-  for (int yb : {2, 4, 1}) {
-    if (yb_env && yb != yb_env) continue;
+  for (int yb : {2, 4, 1}) {  // rows per block: the first tiling that fits
     const int gm = pad_mod((yb + 2) * a.GR, 64, 24), gs = pad_mod(M * gm, 64, 56);
     const int xc = pad_mod32(yb * a.XR, 8), xs = pad_mod32(Cc * xc, 16);
     const size_t bytes = (size_t)4 * (4 * gs + 2 * xs + 4 * 256);  // + a 16-byte dump line per thread
@@ -1505,110 +1431,23 @@ int zf1_setup(Zf1Args& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, 
   }
   if (!a.YB) return TB_ERR_UNSUPPORTED_SIZE;
   a.nyb = (H + a.YB - 1) / a.YB;
-  // z segments: two blocks per CU; ceil(blocks / (2 CUs)) rounds of zlen + 2 plane steps
-  const int base = N * a.nyb;
-  int best = 1 << 30;
-  a.zlen = D;
-  for (int zl = D; zl >= 1; --zl) {
-    const int zs = (D + zl - 1) / zl;
-    const int rounds = (base * zs + 2 * ncu - 1) / (2 * ncu);
-    const int cost = rounds * (zl + 2);
-    if (cost < best) {
-      best = cost;
-      a.zlen = zl;
-    }
-  }
+  a.zlen = tb::zseg(D, N * a.nyb, 2, 2);  // two blocks per CU, two ring-fill planes per segment
   a.ZS = (D + a.zlen - 1) / a.zlen;
   grid = dim3((unsigned)(N * a.nyb * a.ZS));
   return TB_OK;
 }
 
 template <int YB>
-int launch_zf1_t(const Zf1Args& a, size_t lds, dim3 grid, hipStream_t st) {
-  auto kern = a.W <= 128 ? k_conv3d_wgrad_zf1<YB, 32>
-                         : a.W <= 160 ? k_conv3d_wgrad_zf1<YB, 40> : k_conv3d_wgrad_zf1<YB, 64>;
-  const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-  if (attr != hipSuccess) return TB_ERR_HIP;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  return hipGetLastError() == hipSuccess ? TB_OK : TB_ERR_HIP;
+auto zf1_kern(int W) {
+  return W <= 128 ? k_conv3d_wgrad_zf1<YB, 32> : W <= 160 ? k_conv3d_wgrad_zf1<YB, 40> : k_conv3d_wgrad_zf1<YB, 64>;
 }
-
 int launch_zf1(const Zf1Args& a, size_t lds, dim3 grid, hipStream_t st) {
-  return a.YB == 4 ? launch_zf1_t<4>(a, lds, grid, st) : a.YB == 2 ? launch_zf1_t<2>(a, lds, grid, st)
-                                                                    : launch_zf1_t<1>(a, lds, grid, st);
-}
-}  // namespace
-
-// dW (M x Cc x 27, zeroed here) of a 3x3x3 convolution with stride 1 or 2, padding 1 (file header).
-int tb_conv3d_wgrad_f32(const float* G, const float* X, float* dW, int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
-                        int Hi, int Wi, int stride, int pad, void* stream) {
-  if (!G || !X || !dW) return TB_ERR_INVALID_ARG;
-  hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
-  if (pad == 1 && N >= 1 && use_zm(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    ZmArgs z{};
-    size_t lds = 0;
-    dim3 grid;
-    if (zm_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, tb::num_cu()) == TB_OK) {
-      z.G = G; z.X = X; z.dW = dW;
-      if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
-      return launch_zm(z, lds, grid, st0);
-    }
-  }
-  if (pad == 1 && N >= 1 && use_zm2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    Zm2Args z{};
-    size_t lds = 0;
-    dim3 grid;
-    if (zm2_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, tb::num_cu()) == TB_OK) {
-      z.G = G; z.X = X; z.dW = dW;
-      if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
-      return launch_zm2(z, lds, grid, st0);
-    }
-  }
-  if (pad == 1 && N >= 1 && use_zf1(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    Zf1Args z{};
-    size_t lds = 0;
-    dim3 grid;
-    if (zf1_setup(z, lds, grid, N, M, Cc, Do, Ho, Wo, tb::num_cu()) == TB_OK) {
-      z.G = G; z.X = X; z.dW = dW;
-      if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
-      return launch_zf1(z, lds, grid, st0);
-    }
-  }
-  if (pad == 1 && N >= 1 && use_zf2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X)) {
-    Zf2Args z{};
-    int MT = 1;
-    size_t lds = 0;
-    dim3 grid;
-    if (zf2_setup(z, MT, lds, grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, tb::num_cu()) == TB_OK) {
-      z.G = G; z.X = X; z.dW = dW;
-      if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st0) != hipSuccess) return TB_ERR_HIP;
-      return launch_zf2(z, MT, lds, grid, st0);
-    }
-  }
-  WgArgs a{};
-  int seg = 0, TX = 0, by = 0;
-  size_t lds = 0;
-  const int rc = wg_setup(a, seg, TX, by, lds, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
-  if (rc != TB_OK) return rc;
-  a.G = G; a.X = X; a.dW = dW;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st) != hipSuccess) return TB_ERR_HIP;
-  if (TX == 9) {
-    switch (seg) {
-      case 1: return launch_mz<1>(a, lds, st);
-      case 2: return launch_mz<2>(a, lds, st);
-      case 3: return launch_mz<3>(a, lds, st);
-      case 4: return launch_mz<4>(a, lds, st);
-      default: return TB_ERR_UNSUPPORTED_SIZE;
-    }
-  }
-  if (stride == 1) return TX == 1 ? launch_seg<1, 1>(a, seg, by, lds, st) : launch_seg<1, 3>(a, seg, by, lds, st);
-  return TX == 1 ? launch_seg<2, 1>(a, seg, by, lds, st) : launch_seg<2, 3>(a, seg, by, lds, st);
+  auto kern = a.YB == 4 ? zf1_kern<4>(a.W) : a.YB == 2 ? zf1_kern<2>(a.W) : zf1_kern<1>(a.W);
+  return tb::launch_lds(kern, grid, dim3(256), lds, st, a);
 }
 
-// The z-marching route tb_conv3d_wgrad_f32 takes for these sizes, set up for partial tiles: the partial
-// tile of each workgroup is TM x TC x 27 floats (k_wgrad_reduce), `blocks` workgroups per tile.
+// The z-marching route of a call, the one place that picks it.  With a workspace each workgroup writes a
+// partial tile of TM x TC x 27 floats (k_wgrad_reduce), grid.x workgroups per tile; without, float atomics.
 struct ZRoute {
   int kind = 0;  // 0: none (the general kernel, atomics), 1 zm, 2 zm2, 3 zf1, 4 zf2
   ZmArgs zm{};
@@ -1619,33 +1458,77 @@ struct ZRoute {
   size_t lds = 0;
   dim3 grid;
   int TM = 0, TC = 0, ctiles = 1;
+  int YB = 0, zlen = 0, ZS = 0;  // of the chosen route's arguments (the plan query)
   size_t bytes() const { return kind ? (size_t)grid.x * grid.y * TM * TC * 27 * 4 : 0; }
+  template <class A>
+  void take(int k, const A& a, int tm, int tc, int ct) {
+    kind = k, TM = tm, TC = tc, ctiles = ct, YB = a.YB, zlen = a.zlen, ZS = a.ZS;
+  }
 };
 
-static ZRoute zroute(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad,
-                     const void* G, const void* X) {
+bool aligned16(const void* G, const void* X) {
+  return ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(X)) & 15) == 0;
+}
+
+// `aligned`: G and X are 16-byte aligned (the size queries assume it)
+ZRoute zroute(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad,
+              bool aligned = true) {
   ZRoute r;
-  if (pad != 1 || N < 1) return r;
-  const int ncu = tb::num_cu();
-  if (use_zm(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X) &&
-      zm_setup(r.zm, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, ncu) == TB_OK) {
-    r.kind = 1, r.TM = 16, r.TC = 16, r.ctiles = r.zm.ctiles;
-  } else if (use_zm2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X) &&
-             zm2_setup(r.zm2, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, ncu) == TB_OK) {
-    r.kind = 2, r.TM = 32, r.TC = 16, r.ctiles = r.zm2.ctiles;
-  } else if (use_zf1(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X) &&
-             zf1_setup(r.zf1, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, ncu) == TB_OK) {
-    r.kind = 3, r.TM = M, r.TC = Cc, r.ctiles = 1;
-  } else if (use_zf2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi, G, X) &&
-             zf2_setup(r.zf2, r.MT, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, ncu) == TB_OK) {
-    r.kind = 4, r.TM = 16 * r.MT, r.TC = Cc, r.ctiles = 1;
-  }
+  if (pad != 1 || N < 1 || !aligned) return r;
+  if (use_zm(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi) && zm_setup(r.zm, r.lds, r.grid, N, M, Cc, Do, Ho, Wo) == TB_OK)
+    r.take(1, r.zm, 16, 16, r.zm.ctiles);
+  else if (use_zm2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi) &&
+           zm2_setup(r.zm2, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi) == TB_OK)
+    r.take(2, r.zm2, 32, 16, r.zm2.ctiles);
+  else if (use_zf1(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi) &&
+           zf1_setup(r.zf1, r.lds, r.grid, N, M, Cc, Do, Ho, Wo) == TB_OK)
+    r.take(3, r.zf1, M, Cc, 1);
+  else if (use_zf2(M, Cc, stride, Do, Ho, Wo, Di, Hi, Wi) &&
+           zf2_setup(r.zf2, r.MT, r.lds, r.grid, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi) == TB_OK)
+    r.take(4, r.zf2, 16 * r.MT, Cc, 1);
   return r;
+}
+
+template <class A>
+const A& bound(A& a, const float* G, const float* X, float* dW, float* part) {
+  a.G = G, a.X = X, a.dW = dW, a.part = part;
+  return a;
+}
+
+// Launch the route's kernel: partial tiles into `part` (and the zf1 route's bias partials into `bpart`), or
+// float atomics on a zeroed dW where `part` is null.
+int zrun(ZRoute& r, const float* G, const float* X, float* dW, float* part, double* bpart, hipStream_t st) {
+  switch (r.kind) {
+    case 1: return launch_zm(bound(r.zm, G, X, dW, part), r.lds, r.grid, st);
+    case 2: return launch_zm2(bound(r.zm2, G, X, dW, part), r.lds, r.grid, st);
+    case 3: r.zf1.bpart = bpart; return launch_zf1(bound(r.zf1, G, X, dW, part), r.lds, r.grid, st);
+    default: return launch_zf2(bound(r.zf2, G, X, dW, part), r.MT, r.lds, r.grid, st);
+  }
+}
+}  // namespace
+
+// dW (M x Cc x 27, zeroed here) of a 3x3x3 convolution with stride 1 or 2, padding 1 (file header).
+int tb_conv3d_wgrad_f32(const float* G, const float* X, float* dW, int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
+                        int Hi, int Wi, int stride, int pad, void* stream) {
+  if (!G || !X || !dW) return TB_ERR_INVALID_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, aligned16(G, X));
+  WgArgs a{};
+  int seg = 0, TX = 0, by = 0;
+  size_t lds = 0;
+  if (!r.kind) {
+    const int rc = wg_setup(a, seg, TX, by, lds, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
+    if (rc != TB_OK) return rc;
+  }
+  if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)M * Cc * 27, st) != hipSuccess) return TB_ERR_HIP;
+  if (r.kind) return zrun(r, G, X, dW, nullptr, nullptr, st);
+  a.G = G; a.X = X; a.dW = dW;
+  return launch_wg(a, stride, TX, seg, by, lds, st);
 }
 
 int64_t tb_conv3d_wgrad_ws_bytes(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
                                  int pad) {
-  return (int64_t)zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, nullptr, nullptr).bytes();
+  return (int64_t)zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad).bytes();
 }
 
 // the bias partials follow the partial tiles, 8-byte aligned: [grid.x][M] float64 (only the zf1 route)
@@ -1654,7 +1537,7 @@ static size_t bias_bytes(const ZRoute& r, int M) { return r.kind == 3 ? (size_t)
 
 int64_t tb_conv3d_wgrad_bias_ws_bytes(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride,
                                       int pad, int* sums_bias) {
-  const ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, nullptr, nullptr);
+  const ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
   const size_t bb = bias_bytes(r, M);
   if (sums_bias) *sums_bias = bb ? 1 : 0;
   return (int64_t)(bb ? bias_off(r) + bb : r.bytes());
@@ -1666,7 +1549,7 @@ int tb_conv3d_wgrad_bias_ws_f32(const float* G, const float* X, float* dW, float
   if (bias_done) *bias_done = 0;
   if (!G || !X || !dW) return TB_ERR_INVALID_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, G, X);
+  ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, aligned16(G, X));
   if (!ws || !r.kind || ws_bytes < r.bytes() || (reinterpret_cast<uintptr_t>(ws) & 3) != 0)
     return tb_conv3d_wgrad_f32(G, X, dW, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, stream);
   float* part = static_cast<float*>(ws);
@@ -1674,16 +1557,7 @@ int tb_conv3d_wgrad_bias_ws_f32(const float* G, const float* X, float* dW, float
   if (dbias && bias_bytes(r, M) && ws_bytes >= bias_off(r) + bias_bytes(r, M) &&
       (reinterpret_cast<uintptr_t>(ws) & 7) == 0)
     bpart = reinterpret_cast<double*>(static_cast<char*>(ws) + bias_off(r));
-  int rc = TB_OK;
-  switch (r.kind) {
-    case 1: r.zm.G = G, r.zm.X = X, r.zm.dW = dW, r.zm.part = part; rc = launch_zm(r.zm, r.lds, r.grid, st); break;
-    case 2: r.zm2.G = G, r.zm2.X = X, r.zm2.dW = dW, r.zm2.part = part; rc = launch_zm2(r.zm2, r.lds, r.grid, st); break;
-    case 3:
-      r.zf1.G = G, r.zf1.X = X, r.zf1.dW = dW, r.zf1.part = part, r.zf1.bpart = bpart;
-      rc = launch_zf1(r.zf1, r.lds, r.grid, st);
-      break;
-    default: r.zf2.G = G, r.zf2.X = X, r.zf2.dW = dW, r.zf2.part = part; rc = launch_zf2(r.zf2, r.MT, r.lds, r.grid, st); break;
-  }
+  const int rc = zrun(r, G, X, dW, part, bpart, st);
   if (rc != TB_OK) return rc;
   hipLaunchKernelGGL(k_wgrad_reduce, dim3((r.TM * r.TC * 27 + 63) / 64 + (bpart ? 1 : 0), r.grid.y), dim3(1024), 0, st,
                      static_cast<const float*>(part), dW, (int)r.grid.x, r.TM, r.TC, r.ctiles, M, Cc,
@@ -1709,5 +1583,24 @@ int tb_conv3d_wgrad_config(int N, int M, int Cc, int Do, int Ho, int Wo, int Di,
   const int rc = wg_setup(a, seg, TX, by, lds, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
   if (rc != TB_OK) return rc;
   cfg[0] = seg; cfg[1] = TX; cfg[2] = a.YB; cfg[3] = a.nchunks; cfg[4] = (int64_t)lds;
+  return TB_OK;
+}
+
+// The launch tb_conv3d_wgrad_ws_f32 makes for 16-byte aligned operands (no launch):
+// cfg = {kind, YB, zlen, ZS, grid.x, grid.y, LDS bytes, workspace bytes}.
+int tb_conv3d_wgrad_plan(int N, int M, int Cc, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, int pad,
+                         int64_t* cfg) {
+  if (!cfg) return TB_ERR_INVALID_ARG;
+  const ZRoute r = zroute(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
+  WgArgs a{};
+  int seg = 0, TX = 0, by = 0;
+  size_t lds = r.lds;
+  if (!r.kind) {
+    const int rc = wg_setup(a, seg, TX, by, lds, N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad);
+    if (rc != TB_OK) return rc;
+  }
+  cfg[0] = r.kind; cfg[1] = r.kind ? r.YB : a.YB; cfg[2] = r.zlen; cfg[3] = r.ZS;
+  cfg[4] = r.kind ? r.grid.x : wg_grid_x(a, TX, by); cfg[5] = r.kind ? r.grid.y : (unsigned)by;
+  cfg[6] = (int64_t)lds; cfg[7] = (int64_t)r.bytes();
   return TB_OK;
 }

@@ -48,6 +48,7 @@ def _proto(L):
         "tb_kspace_import_f32": (I, [P, P, P, P, I, P, SZ, I, I, P]),
         "tb_conv3d_wgrad_f32": (I, [P, P, P] + [I] * 11 + [P]),
         "tb_conv3d_wgrad_config": (I, [I] * 11 + [P]),
+        "tb_conv3d_wgrad_plan": (I, [I] * 11 + [P]),
         "tb_conv3d_wgrad_ws_bytes": (I64, [I] * 11),
         "tb_conv3d_wgrad_ws_f32": (I, [P, P, P] + [I] * 11 + [P, SZ, P]),
         "tb_conv3d_wgrad_bias_ws_bytes": (I64, [I] * 11 + [P]),

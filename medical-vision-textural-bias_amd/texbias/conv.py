@@ -10,6 +10,7 @@ summed over N, D, H, W -- ATen's generic reduction ran at 0.1-0.3 TB/s, ~7 ms of
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 import os
@@ -38,32 +39,40 @@ def _wgrad_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad) -> int:
     return int(lib().tb_conv3d_wgrad_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad))
 
 
+@functools.lru_cache(maxsize=256)
+def _wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad):
+    sums = ctypes.c_int(0)
+    nb = int(lib().tb_conv3d_wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, ctypes.byref(sums)))
+    return nb, bool(sums.value)
+
+
+def _wgrad(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int, want_bias: bool):
+    """(dW, gb or None) through tb_conv3d_wgrad_bias_ws_f32; the workspace holds the bias partials only where the
+    bias is wanted and the route sums it."""
+    G = G.contiguous()
+    X = X.contiguous()
+    N, M = G.shape[:2]
+    dims = (N, M, X.shape[1], *G.shape[2:], *X.shape[2:], stride, pad)
+    nb, sums = _wgrad_bias_ws_bytes(*dims) if want_bias else (0, False)
+    if not sums:
+        nb = _wgrad_ws_bytes(*dims)
+    dW = torch.empty((M, X.shape[1], 3, 3, 3), dtype=torch.float32, device=G.device)
+    gb = torch.empty(M, dtype=torch.float32, device=G.device) if sums else None
+    ws = torch.empty(nb, dtype=torch.uint8, device=G.device) if nb > 0 else None
+    done = ctypes.c_int(0)
+    with torch.cuda.device(G.device):
+        check(lib().tb_conv3d_wgrad_bias_ws_f32(G.data_ptr(), X.data_ptr(), dW.data_ptr(),
+                                                gb.data_ptr() if sums else None, *dims,
+                                                ws.data_ptr() if ws is not None else None, nb, ctypes.byref(done),
+                                                _stream(G)), "tb_conv3d_wgrad_bias_ws_f32")
+    return dW.view(w_shape), (gb if done.value else None)
+
+
 def wgrad(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int) -> torch.Tensor:
     """dW[m][c][k^3] = corr(G, X) -- see tb_conv3d_wgrad_f32 / tb_conv3d_wgrad_ws_f32 (include/texbias.h): with a
     workspace from the caching allocator the z-marching kernels write per-workgroup partial tiles that one
     reduction sums in order, instead of contended float atomics."""
-    G = G.contiguous()
-    X = X.contiguous()
-    N, M = G.shape[:2]
-    Cc = X.shape[1]
-    dW = torch.empty((M, Cc, 3, 3, 3), dtype=torch.float32, device=G.device)
-    Do, Ho, Wo = G.shape[2:]
-    Di, Hi, Wi = X.shape[2:]
-    nb = _wgrad_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad)
-    ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=G.device) if nb > 0 else None
-    with torch.cuda.device(G.device):
-        check(lib().tb_conv3d_wgrad_ws_f32(G.data_ptr(), X.data_ptr(), dW.data_ptr(), N, M, Cc, Do, Ho, Wo, Di, Hi, Wi,
-                                           stride, pad, ws.data_ptr() if ws is not None else None, nb,
-                                           _stream(G)), "tb_conv3d_wgrad_ws_f32")
-    return dW.view(w_shape)
-
-
-@functools.lru_cache(maxsize=256)
-def _wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad):
-    import ctypes
-    sums = ctypes.c_int(0)
-    nb = int(lib().tb_conv3d_wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, ctypes.byref(sums)))
-    return nb, bool(sums.value)
+    return _wgrad(G, X, w_shape, stride, pad, False)[0]
 
 
 def wgrad_bias(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int):
@@ -71,36 +80,35 @@ def wgrad_bias(G: torch.Tensor, X: torch.Tensor, w_shape, stride: int, pad: int)
     (tb_conv3d_wgrad_bias_ws_f32, include/texbias.h), the bias gradient: (dW, gb) with gb [M] = G summed over the
     batch and the positions, or (dW, None) when the route did not produce it (the caller then takes
     ``channel_sum``)."""
-    import ctypes
-    G = G.contiguous()
-    X = X.contiguous()
-    N, M = G.shape[:2]
-    Cc = X.shape[1]
-    Do, Ho, Wo = G.shape[2:]
-    Di, Hi, Wi = X.shape[2:]
-    nb, sums = _wgrad_bias_ws_bytes(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad)
-    if not sums:
-        return wgrad(G, X, w_shape, stride, pad), None
-    dW = torch.empty((M, Cc, 3, 3, 3), dtype=torch.float32, device=G.device)
-    gb = torch.empty(M, dtype=torch.float32, device=G.device)
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=G.device)
-    done = ctypes.c_int(0)
-    with torch.cuda.device(G.device):
-        check(lib().tb_conv3d_wgrad_bias_ws_f32(G.data_ptr(), X.data_ptr(), dW.data_ptr(), gb.data_ptr(), N, M, Cc, Do, Ho,
-                                                Wo, Di, Hi, Wi, stride, pad, ws.data_ptr(), nb, ctypes.byref(done),
-                                                _stream(G)), "tb_conv3d_wgrad_bias_ws_f32")
-    return dW.view(w_shape), (gb if done.value else None)
+    return _wgrad(G, X, w_shape, stride, pad, True)
+
+
+@functools.lru_cache(maxsize=256)
+def _wgrad_cfg(g_shape, x_shape, stride: int, pad: int):
+    """(return code, cfg) of tb_conv3d_wgrad_config for G [N, M, Do, Ho, Wo] / X [N, Cc, Di, Hi, Wi] (host only)."""
+    cfg = (ctypes.c_int64 * 5)()
+    N, M, Do, Ho, Wo = g_shape
+    Cc, Di, Hi, Wi = x_shape[1:]
+    return lib().tb_conv3d_wgrad_config(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, cfg), tuple(cfg)
 
 
 def wgrad_config(g_shape, x_shape, stride: int, pad: int = 1) -> dict:
     """The tiling ``wgrad`` picks for G [N, M, Do, Ho, Wo] / X [N, Cc, Di, Hi, Wi] (host only,
     tb_conv3d_wgrad_config): SEG, TX, YB, chunks, lds_bytes."""
-    import ctypes
-    cfg = (ctypes.c_int64 * 5)()
+    rc, cfg = _wgrad_cfg(tuple(g_shape), tuple(x_shape), stride, pad)
+    check(rc, "tb_conv3d_wgrad_config")
+    return dict(zip(("SEG", "TX", "YB", "chunks", "lds_bytes"), cfg))
+
+
+def wgrad_plan(g_shape, x_shape, stride: int, pad: int = 1) -> dict:
+    """The launch ``wgrad`` makes for G [N, M, Do, Ho, Wo] / X [N, Cc, Di, Hi, Wi] with 16-byte aligned operands
+    (host only, tb_conv3d_wgrad_plan): kind (0: the general kernel, 1 zm, 2 zm2, 3 zf1, 4 zf2), YB, zlen, ZS,
+    grid_x, grid_y, lds_bytes, ws_bytes."""
+    cfg = (ctypes.c_int64 * 8)()
     N, M, Do, Ho, Wo = g_shape
     Cc, Di, Hi, Wi = x_shape[1:]
-    check(lib().tb_conv3d_wgrad_config(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, cfg), "tb_conv3d_wgrad_config")
-    return dict(zip(("SEG", "TX", "YB", "chunks", "lds_bytes"), list(cfg)))
+    check(lib().tb_conv3d_wgrad_plan(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, pad, cfg), "tb_conv3d_wgrad_plan")
+    return dict(zip(("kind", "YB", "zlen", "ZS", "grid_x", "grid_y", "lds_bytes", "ws_bytes"), cfg))
 
 
 def channel_sum(g: torch.Tensor) -> torch.Tensor:
@@ -123,15 +131,10 @@ def custom_backward_applies(x: torch.Tensor, w: torch.Tensor) -> bool:
     return ENABLED and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
 
 
-@functools.lru_cache(maxsize=256)
 def _wgrad_tiles(g_shape, x_shape, stride: int) -> bool:
     """A tiling of tb_conv3d_wgrad_f32 exists for these shapes (tb_conv3d_wgrad_config, host only):
     rows too wide for the LDS budget at the channel tile go to ATen instead of failing."""
-    import ctypes
-    cfg = (ctypes.c_int64 * 5)()
-    N, M, Do, Ho, Wo = g_shape
-    Cc, Di, Hi, Wi = x_shape[1:]
-    return lib().tb_conv3d_wgrad_config(N, M, Cc, Do, Ho, Wo, Di, Hi, Wi, stride, 1, cfg) == 0
+    return _wgrad_cfg(tuple(g_shape), tuple(x_shape), stride, 1)[0] == 0
 
 
 def weight_grad(gy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, stride: int, transposed: bool = False,
@@ -173,13 +176,13 @@ def fast_wgrad_applies(x: torch.Tensor, w: torch.Tensor, out_spatial, stride, pa
         g_shape, x_shape = (x.shape[0], w.shape[0]) + tuple(out_spatial), tuple(x.shape)
     # the z-marching kernels (partial tiles, no atomics) take any reduction length; the general split-K
     # kernel only long ones
-    if ZMARCH_MIN_POS and pos_of(x, out_spatial, transposed) >= ZMARCH_MIN_POS and \
+    pos = pos_of(x, out_spatial, transposed)
+    if ZMARCH_MIN_POS and pos >= ZMARCH_MIN_POS and \
             _wgrad_ws_bytes(*g_shape[:2], x_shape[1], *g_shape[2:], *x_shape[2:], s, 1) > 0 and \
             _wgrad_tiles(g_shape, x_shape, s):
         # (the workspace query assumes 16-B aligned operands; a misaligned call falls back to the atomic
         # split-K kernel inside the library, which needs a tiling of its own)
         return True
-    pos = x.shape[0] * math.prod(out_spatial if not transposed else x.shape[2:])
     if pos < MIN_K_PER_OUTPUT * w.shape[0] * w.shape[1] * 27 // 16:
         return False
     return _wgrad_tiles(g_shape, x_shape, s)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time tb_conv3d_small_f32 (the top ResidualUnit's 3->3 conv, 2 x 3 x 240 x 240 x 160) with HIP events,
-median of 10.  Diagnostic; TEXBIAS_SMALL_CONV_Z=0 selects the per-plane kernel."""
+median of 10.  Diagnostic; the library picks the kernel (no switch)."""
 import os
 import sys
 

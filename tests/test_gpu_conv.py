@@ -178,3 +178,34 @@ def test_wgrad_partial_tiles_match_atomics(conv, M, Cc, N, gsp, xsp, stride):
     assert (outs[0] - ref).abs().max().item() <= 1e-5 * scale
     assert torch.equal(outs[0], outs[1])
     assert (small - ref).abs().max().item() <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("M,Cc,gsp,xsp,stride", [(16, 16, (3, 5, 8), (3, 5, 8), 1), (32, 16, (3, 4, 8), (6, 8, 16), 2)])
+def test_wgrad_ws_misaligned_x_takes_general_kernel(conv, M, Cc, gsp, xsp, stride):
+    """tb_conv3d_wgrad_ws_f32 with a valid workspace but an X that is 4-byte and not 16-byte aligned (a
+    one-float-offset view of a larger buffer): the z-marching route the plan names for aligned operands does not
+    apply, the general kernel runs, and dW meets the float64 bar e <= 4 max(e_ATen32, 1e-6 scale)."""
+    from texbias._lib import lib
+    torch.manual_seed(9)
+    G = torch.randn((1, M) + gsp, device="cuda")
+    buf = torch.randn(1 + Cc * xsp[0] * xsp[1] * xsp[2], device="cuda")
+    X = buf[1:].view((1, Cc) + xsp)
+    assert X.data_ptr() % 16 == 4 and G.data_ptr() % 16 == 0
+    assert conv.wgrad_plan(tuple(G.shape), tuple(X.shape), stride)["kind"] == stride  # aligned: zm / zm2
+    dims = (1, M, Cc) + gsp + xsp + (stride, 1)
+    nb = int(lib().tb_conv3d_wgrad_ws_bytes(*dims))
+    assert nb > 0
+    ws = torch.full((nb // 4,), float("nan"), device="cuda")
+    ours = torch.empty((M, Cc, 3, 3, 3), device="cuda")
+    assert lib().tb_conv3d_wgrad_ws_f32(G.data_ptr(), X.data_ptr(), ours.data_ptr(), *dims, ws.data_ptr(), nb,
+                                        torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert torch.isnan(ws).all(), "the general kernel leaves the workspace alone"
+    w = torch.zeros_like(ours, requires_grad=True)
+    ref, = torch.autograd.grad(torch.nn.functional.conv3d(X, w, stride=stride, padding=1), w, G)
+    w64 = torch.zeros_like(ours, dtype=torch.float64, requires_grad=True)
+    r64, = torch.autograd.grad(torch.nn.functional.conv3d(X.double(), w64, stride=stride, padding=1), w64, G.double())
+    scale = r64.abs().max().item()
+    e, er = (ours.double() - r64).abs().max().item(), (ref.double() - r64).abs().max().item()
+    print(f"max|ours - r64| {e:.3e}  max|ATen - r64| {er:.3e}  scale {scale:.3e}")
+    assert e <= 4 * max(er, 1e-6 * scale)

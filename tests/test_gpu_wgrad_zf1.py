@@ -24,6 +24,13 @@ def conv(gpu):
     return C
 
 
+def test_uneven_z_plan(conv):
+    """The plan the "uneven-z" shape relies on (SHAPES' comment), from the planner itself."""
+    (M, Cc), (N, D, H, W) = SHAPES[IDS.index("uneven-z")]
+    p = conv.wgrad_plan((N, M, D, H, W), (N, Cc, D, H, W), 1)
+    assert (p["kind"], p["YB"], p["zlen"], p["ZS"]) == (3, 2, 3, 10) and D % p["zlen"] == 1
+
+
 @pytest.fixture(scope="module")
 def cases(conv):
     """Per shape, computed once: inputs, two calls of wgrad_bias, and the float64 / ATen float32 references."""
