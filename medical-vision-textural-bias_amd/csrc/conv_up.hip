@@ -1369,8 +1369,205 @@ __global__ __launch_bounds__(NTH) void k_conv3d_mfma_s1(S1Args a) {  // (NWG pha
 }
 }  // namespace
 
+// ------------------------------------------------- the same conv in split precision on the bf16 matrix cores
+// k_conv3d_mfma_s1's product on v_mfma_f32_16x16x32_bf16 (split_bf16.h), staged as k_conv16_split stages:
+// k = (tap, channel), one 32-k step = two taps x the 16 channels of one channel group, tap 27 with zero
+// weights.  8 waves; wave w holds the A fragments of (output tile mt, channel group grp) = (w / G % MTB,
+// w % G) for the kernel's life (14 steps x 3 parts, 168 registers, split once at start-up; flip reads
+// W[c][m][26 - t]) and takes the position tiles h, h + NWG, .. of a step (h = w / (G MTB), NWG = 8 / (G
+// MTB) waves per role), one at a time with step q + 1's B fragments read ahead of step q's six MFMAs.
+// Positions are the flattened (row, column) of the block's YB rows.  LDS: a 3-slot plane ring of bf16 part
+// images [slot][part][group][row 0..YB + 1][position 0..W + 4][16 ch] (position = x + 1, 32 B each, W + 5
+// positions: a row pitch of 8 dwords mod 32 as in k_conv16_split, one ds_read_b128 per part), then the
+// partial tiles [tile][role][lane] as the accumulator's own float4 (one ds_write_b128 / ds_read_b128 per
+// lane, no bank shared), then the block's bias values.  A staging task (group, x quad, row, channel quad)
+// loads four float4 a step ahead and splits them at the LDS store, rows and planes outside the volume
+// masked to zero there.  Step z: fetch plane z + 2 | per tile 84 MFMAs, hi + lo to the partials | barrier |
+// plane z + 2 over plane z - 1's slot; per (tile, output tile) the G partials summed in group order, then
+// the bias, then `add`, and stored | barrier.  No atomics: the order is fixed.
+namespace {
+struct XSArgs {
+  const float* x;     // [N][C][D][H][W]
+  const float* W;     // [C m][C c][27]
+  const float* bias;  // [C] or null
+  const float* add;   // summed into y (y's layout), or null
+  float* y;
+  int D, H, Wd, YB;
+  int ZS, zlen, nyb, MG;  // z segments, row blocks, output-tile groups
+  int ntile;              // position tiles per step: ceil(YB W / 16)
+  int flip;               // 1: the input gradient, A = W[c][m][26 - t]
+  int64_t addsn;          // floats between samples of `add` (0: contiguous)
+};
+
+inline size_t xs_slot(int G, int YB, int W) { return (size_t)3 * G * (YB + 2) * (W + 5) * 32; }  // bytes per plane slot
+
+template <int G, int MTB, bool ADD>
+__global__ __launch_bounds__(512) void k_conv_mfma_split(XSArgs a) {
+  using tb::bf16x8;
+  constexpr int CIN = 16 * G, NTH = 512, NWV = NTH / 64, NROLE = G * MTB, NWG = NWV / NROLE;
+  static_assert(NROLE * NWG == NWV, "every wave has a role");
+  extern __shared__ __attribute__((aligned(16))) char ringx[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = w % G, mt = (w / G) % MTB, h = w / NROLE;
+  const int D = a.D, H = a.H, Wd = a.Wd, YB = a.YB, NR = YB + 2;
+  const int RPB = (Wd + 5) * 32, GPB = NR * RPB, SPL = G * GPB, SLOT = 3 * SPL;  // bytes: row, group, part, slot
+  char* part = ringx + 3 * SLOT;                                                 // [ntile][NROLE][64] float4
+  float* bsm = reinterpret_cast<float*>(part + a.ntile * NROLE * 1024);          // [MTB * 16]
+  for (int i = tid; i < 3 * SLOT / 16; i += NTH) reinterpret_cast<uint4*>(ringx)[i] = make_uint4(0, 0, 0, 0);
+  int b = (int)blockIdx.x;
+  const int zs = b % a.ZS;
+  b /= a.ZS;
+  const int mg = b % a.MG;
+  b /= a.MG;
+  const int yb = b % a.nyb, n = b / a.nyb;
+  const int COUT = 16 * MTB * a.MG;
+  const int y0 = yb * YB;
+  const int z0 = zs * a.zlen, z1 = min(D, z0 + a.zlen);
+  if (tid < MTB * 16) bsm[tid] = a.bias ? a.bias[mg * MTB * 16 + tid] : 0.f;
+  // A: lane (m = l & 15, g4 = l >> 4), step q: tap 2 q + (g4 >> 1), channels 16 grp + 8 (g4 & 1) + j
+  const int li = lane & 15, g4 = lane >> 4, hi = g4 >> 1;
+  const int m0 = (mg * MTB + mt) * 16;
+  bf16x8 af[14][3];
+  {
+    const int wsm = a.flip ? 27 : CIN * 27, wsc = a.flip ? CIN * 27 : 27;  // W[m][c][t], flipped W[c][m][26 - t]
+    const float* wl = a.W + (m0 + li) * wsm + (16 * grp + 8 * (g4 & 1)) * wsc;
+#pragma unroll
+    for (int q = 0; q < 14; ++q) {
+      const int t = 2 * q + hi, tc = t < 27 ? t : 26;
+      const float* wq = wl + (a.flip ? 26 - tc : tc);
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = wq[j * wsc];
+      if (q == 13) {  // tap 27 does not exist: zero weights (the B operand there is tap 26's, finite)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = hi ? 0.f : v[j];
+      }
+      tb::split3(v, af[q][0], af[q][1], af[q][2]);
+    }
+  }
+  const int64_t plane = (int64_t)H * Wd, cstride = (int64_t)D * plane;
+  const char* xb = reinterpret_cast<const char*>(a.x + (int64_t)n * CIN * cstride);
+  // this thread's staging task (channel quad fastest, then row, x quad, group); threads past the last task
+  // load the sample's first floats and write zeros over the spare positions W + 1 .. W + 4 of row 0
+  const int W4 = Wd >> 2;
+  const int cq = tid & 3, rr = (tid >> 2) % NR, r2 = (tid >> 2) / NR, q4 = r2 % W4, sg = r2 / W4;
+  const bool act = sg < G;
+  const int lof = act ? sg * GPB + rr * RPB + (4 * q4 + 1) * 32 + cq * 8 : (Wd + 1) * 32;
+  const int yi = y0 - 1 + rr;
+  const bool rowok = act && yi >= 0 && yi < H;
+  // per-lane byte offsets (32 bits: the host keeps a sample below 2 GiB) on wave-uniform bases
+  const unsigned chb = (unsigned)(4 * cstride);
+  const unsigned gof = rowok ? (unsigned)(16 * sg + 4 * cq) * chb + 4u * (unsigned)(yi * Wd + 4 * q4) : 0u;
+  float4 rg[4];
+  auto load = [&](int zi) {  // nothing conditional; zeroed by the mask at the store
+    const char* src = xb + (int64_t)(zi < 0 ? 0 : zi >= D ? D - 1 : zi) * plane * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) rg[c] = *reinterpret_cast<const float4*>(src + c * chb + gof);
+  };
+  auto store = [&](int zi) {
+    char* d = ringx + ((zi + 3) % 3) * SLOT + lof;
+    const unsigned m = 0u - (unsigned)(rowok && zi >= 0 && zi < D);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        v[c] = __uint_as_float(__float_as_uint(e == 0 ? rg[c].x : e == 1 ? rg[c].y : e == 2 ? rg[c].z : rg[c].w) & m);
+      unsigned p[3][2];
+      tb::split3_pk(v[0], v[1], p[0][0], p[1][0], p[2][0]);
+      tb::split3_pk(v[2], v[3], p[0][1], p[1][1], p[2][1]);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) *reinterpret_cast<uint2*>(d + s * SPL + e * 32) = make_uint2(p[s][0], p[s][1]);
+    }
+  };
+  __syncthreads();
+  load(z0 - 1);
+  store(z0 - 1);
+  load(z0);
+  store(z0);
+  load(z0 + 1);
+  store(z0 + 1);
+  // every start-up load (weights, bias, the first planes) retired here: no vmcnt(0) ahead of a step's MFMAs
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __syncthreads();
+  const int npos = YB * Wd, ntile = a.ntile;
+  float* ybase = a.y + (int64_t)n * COUT * cstride;
+  const float* abase = ADD ? a.add + (int64_t)n * (a.addsn ? a.addsn : COUT * cstride) : nullptr;
+  const int lb = grp * GPB + 16 * (g4 & 1);  // B lane base: the wave's group, channel half g4 & 1
+  for (int z = z0; z < z1; ++z) {
+    load(z + 2);
+    int hv = hi;  // opaque: the per-step B offsets it selects are recomputed, not kept in 14 registers
+    asm volatile("" : "+v"(hv));
+    int sb[3];  // byte offsets of planes z - 1, z, z + 1
+#pragma unroll
+    for (int tz = 0; tz < 3; ++tz) sb[tz] = ((z + tz + 2) % 3) * SLOT;
+    for (int t = h; t < ntile; t += NWG) {
+      const int p = 16 * t + li, pc = p < npos ? p : npos - 1;  // past the last position: the last one's values
+      const int yy = pc / Wd, xx = pc - yy * Wd;
+      const char* rb = ringx + lb + yy * RPB + xx * 32;
+      bf16x8 bq[2][3];
+      auto ldb = [&](int q, bf16x8 (&bf)[3]) {  // read in the order the products take them: parts 1, 2, 0
+        const int t0 = 2 * q, t1 = 2 * q + 1 < 27 ? 2 * q + 1 : 26;
+        const int c0 = sb[t0 / 9] + ((t0 / 3) % 3) * RPB + (t0 % 3) * 32;
+        const int c1 = sb[t1 / 9] + ((t1 / 3) % 3) * RPB + (t1 % 3) * 32;
+        const int o = hv ? c1 : c0;
+        bf[1] = *reinterpret_cast<const bf16x8*>(rb + o + SPL);
+        bf[2] = *reinterpret_cast<const bf16x8*>(rb + o + 2 * SPL);
+        bf[0] = *reinterpret_cast<const bf16x8*>(rb + o);
+      };
+      tb::f32x4s c = {0.f, 0.f, 0.f, 0.f}, cs = c;  // leading / small products
+      ldb(0, bq[0]);
+#pragma unroll
+      for (int q = 0; q < 14; ++q) {
+        if (q + 1 < 14) ldb(q + 1, bq[(q + 1) & 1]);
+        tb::mfma_split6(af[q], bq[q & 1], c, cs);
+      }
+      c += cs;
+      // schedule: step q + 1's three reads, then step q's six MFMAs
+      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+      for (int q = 0; q < 13; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+      *reinterpret_cast<tb::f32x4s*>(part + ((t * NROLE + mt * G + grp) * 64 + lane) * 16) = c;
+    }
+    __syncthreads();
+    store(z + 2);  // unconditionally (after the last step a dead slot)
+    // (position tile, output tile) combos over the waves: the G groups' partials in group order, the bias, `add`
+    for (int k = w; k < ntile * MTB; k += NWV) {
+      const int t = k / MTB, mq = k - t * MTB;
+      const int p = 16 * t + li, pc = p < npos ? p : npos - 1;
+      const int yy = pc / Wd, xx = pc - yy * Wd;
+      const bool ok = p < npos && y0 + yy < H;
+      const int mb = (mg * MTB + mq) * 16 + 4 * g4;
+      // C: column = position li, rows m = 4 g4 + r; 32-bit float offsets on the plane's base
+      const unsigned oo = (unsigned)(mb * cstride + (int64_t)min(y0 + yy, H - 1) * Wd + xx);
+      float av[4];
+      if constexpr (ADD) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) av[r] = (abase + (int64_t)z * plane)[oo + (unsigned)r * (unsigned)cstride];
+      }
+      const char* pr = part + ((t * NROLE + mq * G) * 64 + lane) * 16;
+      tb::f32x4s v = *reinterpret_cast<const tb::f32x4s*>(pr);
+#pragma unroll
+      for (int gg = 1; gg < G; ++gg) v += *reinterpret_cast<const tb::f32x4s*>(pr + gg * 1024);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float o = v[r] + bsm[mq * 16 + 4 * g4 + r];
+        if constexpr (ADD) o += av[r];
+        if (ok) (ybase + (int64_t)z * plane)[oo + (unsigned)r * (unsigned)cstride] = o;
+      }
+    }
+    __syncthreads();
+  }
+}
+}  // namespace
+
 // Conv3d(C -> C, 3, stride 1, padding 1) forward for C = 32 or 64: x [N][C][D][H][W] -> y, W % 4 == 0,
-// W <= 64; weight [C][C][27], bias [C] or NULL.  (csrc/conv_up.hip, k_conv3d_mfma_s1)
+// W <= 64; weight [C][C][27], bias [C] or NULL.  (csrc/conv_up.hip, k_conv_mfma_split / k_conv3d_mfma_s1)
 int tb_conv3d_mfma_f32(const float* x, const float* W, const float* bias, float* y, int N, int C, int D, int H, int Wd,
                        void* stream) {
   return tb_conv3d_mfma_add_f32(x, W, bias, nullptr, y, N, C, D, H, Wd, stream);
@@ -1389,11 +1586,46 @@ int tb_conv3d_mfma_dgrad_f32(const float* gy, const float* W, const float* add, 
   return mfma_call(gy, W, nullptr, add, dx, N, C, D, H, Wd, 1, stream, add_sn);
 }
 
+// The split kernel's plan for a shape, false where it does not serve it: C = 32 puts both output tiles in
+// the block (MTB 2, two waves per role), C = 64 one (MTB 1, two waves per role, 4 block groups).  Rows per
+// step: the most, up to 4, whose staging tasks fit the block's 512 threads and whose 3-slot ring, partial
+// tiles and bias fit 160 KiB.  C = 32 rows narrower than 16 stay on the f32 kernel: at W = 8 the split form
+// measured slower without `add` (42.7 against 39.0 us forward at 2 x 32 x 32 x 32 x 8; W = 12 not measured).
+static bool xs_plan(int C, int D, int H, int Wd, XSArgs& s, size_t& lds) {
+  if ((int64_t)C * D * H * Wd >= (1LL << 29) || (C == 32 && Wd < 16)) return false;
+  const int G = C / 16, MTB = G == 2 ? 2 : 1;
+  for (int YB = std::min(4, H); YB >= 1; --YB) {
+    const int ntile = (YB * Wd + 15) / 16;
+    lds = 3 * xs_slot(G, YB, Wd) + (size_t)ntile * G * MTB * 1024 + MTB * 64;
+    if (4 * G * (YB + 2) * (Wd / 4) > 512 || lds > 163840) continue;
+    s.D = D, s.H = H, s.Wd = Wd, s.YB = YB, s.ntile = ntile;
+    s.nyb = (H + YB - 1) / YB;
+    s.MG = C / (16 * MTB);
+    return true;
+  }
+  return false;
+}
+
 static int mfma_call(const float* x, const float* W, const float* bias, const float* add, float* y, int N, int C, int D,
                      int H, int Wd, int flip, void* stream, int64_t add_sn) {
   if (!x || !W || !y || N < 1 || D < 1 || H < 1 || Wd < 1) return TB_ERR_INVALID_ARG;
   if ((C != 32 && C != 64) || Wd % 4 != 0 || Wd > 64 || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
     return TB_ERR_UNSUPPORTED_SIZE;
+  // k_conv_mfma_split where its plan exists (xs_plan: the ring and the partial tiles within the LDS, one
+  // staging task per thread, samples below 2 GiB for the 32-bit byte offsets); k_conv3d_mfma_s1 otherwise
+  {
+    XSArgs s{};
+    size_t slds = 0;
+    if (xs_plan(C, D, H, Wd, s, slds)) {
+      s.x = x, s.W = W, s.bias = bias, s.add = add, s.y = y, s.flip = flip, s.addsn = add_sn;
+      s.zlen = tb::zseg(D, N * s.nyb * s.MG, 1, 2);  // 8 waves at 2 per SIMD: one block per CU
+      s.ZS = (D + s.zlen - 1) / s.zlen;
+      void (*sk)(XSArgs) = C == 32 ? (add ? k_conv_mfma_split<2, 2, true> : k_conv_mfma_split<2, 2, false>)
+                                   : (add ? k_conv_mfma_split<4, 1, true> : k_conv_mfma_split<4, 1, false>);
+      return tb::launch_lds(sk, dim3((unsigned)(N * s.nyb * s.MG * s.ZS)), dim3(512), slds,
+                            reinterpret_cast<hipStream_t>(stream), s);
+    }
+  }
   // 4 waves with 5 chains each (8 waves, two per role on alternate tiles with 3 chains, measured
   // slower here, 245 vs 211 us at 32 -> 32, unlike k_conv3d_fwd16).  (Persistent step
   // shares as in k_conv3d_fwd16 measured no gain at 32 -> 32, 186 vs 184 us, and the loop they need cost
