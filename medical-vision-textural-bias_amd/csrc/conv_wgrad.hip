@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "conv_host.h"
+#include "split_bf16.h"
 #include "texbias.h"
 
 namespace {
@@ -500,6 +501,251 @@ __global__ __launch_bounds__(64 * NW) void k_conv3d_wgrad_zm(ZmArgs a) {
     const float v = red[((j * 2 + 0) * 4 + rr) * 64 + ln] + red[((j * 2 + 1) * 4 + rr) * 64 + ln];
     if (pt) {
       pt[(m * 16 + c) * 27 + j] = v;  // the whole tile (zeros past mv, cv: those G / X rows were staged as 0)
+    } else if (m < mv && c < cv) {
+      atomicAdd(&a.dW[((int64_t)(m0 + m) * a.Cc + (c0 + c)) * 27 + j], v);
+    }
+  }
+}
+
+// k_conv3d_wgrad_zm in split precision on the bf16 matrix cores (split_bf16.h): the same march, ring, f32 LDS
+// image, staging and single barrier per z step under the same ZmArgs, and the operands are split at the
+// read.  A k-step is 32 positions: the plane's YB W positions are 4-groups g = yy W/4 + q (G rows are
+// contiguous in LDS, so group g is at 4 g; an X row starts PX - W floats later per row), lane group lk
+// of step s takes groups 8 s + 2 lk and + 1 (YB W / 4 is even: a lane's groups are both inside or both
+// past the plane; past it the X values are replaced by zeros).  27 taps x (hi, lo) do not fit a wave, so
+// the 12 waves are (ty = wave % 3, every fourth step from wave / 3): a wave splits the three G planes'
+// fragments (12 split3_pk) and its one X row's (6 split3_pk for cols 4 q + 1 .. 4 q + 6 of both groups, or,
+// with W % 8 == 0, where a lane's groups are neighbours in one row, 5 for cols 4 q + 1 .. 4 q + 10; the
+// tx = 1 fragment's pairs are v_alignbit of their neighbours) for 9 taps x 6 MFMAs per step.
+// hi + lo once at the end; waves 6..11 hand their sums to 0..5 through the same 2-slot image as above.
+template <int YB, int WV, bool EVEN>  // WV: most float4 per row (W <= 4 WV); EVEN: W % 8 == 0
+__global__ __launch_bounds__(768) void k_conv3d_wgrad_zm_split(ZmArgs a) {
+  constexpr int NT = 768;
+  constexpr int NXR = YB + 2;  // staged X rows
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int W = a.W, H = a.H, D = a.D, W4 = a.W4;
+  const int GS = 16 * a.MS, XS = 16 * a.RX;  // slab sizes
+  float* gsl = smem;                        // [4 slots][16 m][MS]: row yy at yy * W4, zero past W
+  float* xsl = smem + 4 * GS;               // [2 slots][16 c][RX]: row r at r * PX, x at col x + 2
+  const int tile = (int)blockIdx.y, mt = tile / a.ctiles, ct = tile - mt * a.ctiles;
+  int b = (int)blockIdx.x;
+  const int zs = b % a.ZS;
+  b /= a.ZS;
+  const int yb = b % a.nyb, n = b / a.nyb;
+  const int m0 = 16 * mt, c0 = 16 * ct;
+  const int mv = min(16, a.M - m0), cv = min(16, a.Cc - c0);
+  const int y0 = yb * YB;
+  const int z0 = zs * a.zlen, z1 = min(D, z0 + a.zlen);
+  for (int i = tid; i < 4 * GS + 2 * XS; i += NT) smem[i] = 0.f;  // halos, pads, absent rows stay 0
+  const int64_t plane = (int64_t)H * W;
+  const float* Gb = a.G + ((int64_t)n * a.M + m0) * D * plane;
+  const float* Xb = a.X + ((int64_t)n * a.Cc + c0) * D * plane;
+  // staging items: a thread keeps one (row, float4 column) of the slab and takes every XCP-th / GCP-th
+  // channel from its first, so an item's global and LDS offsets are the first one's plus a uniform step
+  // (k_conv3d_wgrad_zm's per-item offsets cost 10 registers this kernel does not have); bit j of xok /
+  // gok: item j exists (channel < cv / mv, row inside the plane)
+  const int W4v = W >> 2;
+  constexpr int NXL = (16 + NT / (NXR * WV) - 1) / (NT / (NXR * WV)), NGL = (16 + NT / (YB * WV) - 1) / (NT / (YB * WV));
+  const int xcp = NT / (NXR * W4v), gcp = NT / (YB * W4v);  // channels per pass
+  const int64_t plane4 = plane / 4;
+  int xg0, gg0, lof, xok = 0, gok = 0;  // lof: the LDS offsets, X's | G's << 16 (both below 2^16 floats)
+  {
+    const int q = tid % W4v, t = tid / W4v, r = t % NXR, c = t / NXR;
+    const int y = y0 - 1 + r;
+    xg0 = (int)((int64_t)c * D * plane4) + (y * W + 4 * q) / 4;  // in float4 of the plane-0 base
+    lof = c * a.RX + r * a.PX + 2 + 4 * q;
+#pragma unroll
+    for (int j = 0; j < NXL; ++j)
+      if (c < xcp && c + xcp * j < cv && y >= 0 && y < H) xok |= 1 << j;
+  }
+  {
+    const int q = tid % W4v, t = tid / W4v, yy = t % YB, m = t / YB;
+    const int y = y0 + yy;
+    gg0 = (int)((int64_t)m * D * plane4) + (y * W + 4 * q) / 4;
+    lof |= (m * a.MS + yy * W4 + 4 * q) << 16;
+#pragma unroll
+    for (int j = 0; j < NGL; ++j)
+      if (m < gcp && m + gcp * j < mv && y < H) gok |= 1 << j;
+  }
+  const int ok = xok | gok << 8;
+  const int xgs = (int)((int64_t)xcp * D * plane4), xls = xcp * a.RX;
+  const int ggs = (int)((int64_t)gcp * D * plane4), gls = gcp * a.MS;
+  float4 rx[NXL], rg[NGL];
+  // (zero-selects at the LDS store, not at the load: see k_conv3d_wgrad_zm)
+  auto load_x = [&](int zi) {
+    const float4* src = reinterpret_cast<const float4*>(Xb) + (int64_t)zi * plane4;
+#pragma unroll
+    for (int j = 0; j < NXL; ++j) rx[j] = src[(ok >> j) & 1 ? xg0 + j * xgs : 0];
+  };
+  auto store_x = [&](int slot) {
+    float* d = xsl + slot * XS;
+#pragma unroll
+    for (int j = 0; j < NXL; ++j)
+      if ((ok >> j) & 1) {
+        float2* p = reinterpret_cast<float2*>(d + (lof & 0xffff) + j * xls);
+        p[0] = make_float2(rx[j].x, rx[j].y);
+        p[1] = make_float2(rx[j].z, rx[j].w);
+      }
+  };
+  bool gin = false;             // the G plane in rg lies inside [0, D) (else stored as zeros)
+  auto load_g = [&](int pz) {  // G plane pz (zero outside [0, D))
+    gin = pz >= 0 && pz < D;
+    const float4* src = reinterpret_cast<const float4*>(Gb) + (int64_t)(gin ? pz : 0) * plane4;
+#pragma unroll
+    for (int j = 0; j < NGL; ++j) rg[j] = src[(ok >> (8 + j)) & 1 ? gg0 + j * ggs : 0];
+  };
+  auto store_g = [&](int slot) {
+    float* d = gsl + slot * GS;
+#pragma unroll
+    for (int j = 0; j < NGL; ++j)
+      if ((ok >> (8 + j)) & 1) {
+        const float4 v = gin ? rg[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float2* p = reinterpret_cast<float2*>(d + (lof >> 16) + j * gls);
+        p[0] = make_float2(v.x, v.y);
+        p[1] = make_float2(v.z, v.w);
+      }
+  };
+  __syncthreads();  // the zero fill is done before any slab store
+  load_g(z0 - 1);
+  store_g((z0 + 3) & 3);
+  load_g(z0);
+  store_g(z0 & 3);
+  load_x(z0);
+  load_g(z0 + 1);
+
+  const int li = lane & 15, lk = lane >> 4;
+  const int ty = wave % 3, sp = wave / 3;
+  const int NG = YB * W4v, nsteps = (NG + 7) >> 3;  // 4-groups and 32-position steps per plane
+  const int rskip = a.PX - W;                        // X row pitch beyond the G row pitch
+  tb::f32x4s hi[9], lo[9];                           // [tz][tx]
+#pragma unroll
+  for (int j = 0; j < 9; ++j) hi[j] = lo[j] = tb::f32x4s{0.f, 0.f, 0.f, 0.f};
+  for (int zi = z0; zi < z1; ++zi) {
+    store_x(zi & 1);
+    store_g((zi + 1) & 3);
+    __syncthreads();  // as in k_conv3d_wgrad_zm
+    load_x(zi + 1 < D ? zi + 1 : zi);
+    load_g(zi + 2);
+    int lv = li;
+    asm volatile("" : "+v"(lv));  // li * MS, li * RX are made per plane: held across the k loop they spill
+    const int aoff = lv * a.MS;
+    const int boff = lv * a.RX + ty * a.PX;  // X[c = li][row yy + ty], col 0
+    const float* gp[3] = {gsl + ((zi + 1) & 3) * GS + aoff, gsl + (zi & 3) * GS + aoff,
+                          gsl + ((zi + 3) & 3) * GS + aoff};  // tz = 0, 1, 2: planes zi + 1, zi, zi - 1
+    const float* xb = xsl + (zi & 1) * XS + boff;
+    for (int s = sp; s < nsteps; s += 4) {
+      const int g0 = 8 * s + 2 * lk;
+      const bool in = EVEN || g0 < NG;  // (W % 8 == 0: whole steps only, and a lane's groups share a row)
+      const int ga = in ? g0 : 0, gb = ga + 1;
+      // B: cols 4 q .. of each group's row (8-byte aligned), of which 4 q + 1 .. 4 q + 6 are x - 1 .. x + 4
+      tb::bf16x8 bf[3][3];  // [tx][part]
+      if constexpr (EVEN) {
+        int row = 0;
+#pragma unroll
+        for (int r = 1; r < YB; ++r) row += ga >= r * W4v ? 1 : 0;
+        const float2* src = reinterpret_cast<const float2*>(xb + 4 * ga + rskip * row);
+        float2 v[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v[i] = src[i];
+        unsigned p[5][3], sh[4][3];  // pairs of cols (1,2) (3,4) .. (9,10), and (2,3) .. (8,9)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) tb::split3_pk(v[i].y, v[i + 1].x, p[i][0], p[i][1], p[i][2]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) sh[i][q] = __builtin_amdgcn_alignbit(p[i + 1][q], p[i][q], 16);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          bf[0][q] = __builtin_bit_cast(tb::bf16x8, u32x4{p[0][q], p[1][q], p[2][q], p[3][q]});
+          bf[1][q] = __builtin_bit_cast(tb::bf16x8, u32x4{sh[0][q], sh[1][q], sh[2][q], sh[3][q]});
+          bf[2][q] = __builtin_bit_cast(tb::bf16x8, u32x4{p[1][q], p[2][q], p[3][q], p[4][q]});
+        }
+      } else {
+        unsigned p[2][5][3];  // [group][pair 01, 23, 45, 12, 34][part]
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int g = h ? gb : ga;
+          int row = 0;
+#pragma unroll
+          for (int r = 1; r < YB; ++r) row += g >= r * W4v ? 1 : 0;
+          const float2* src = reinterpret_cast<const float2*>(xb + 4 * g + rskip * row);
+          float2 v[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            v[i] = src[i];
+            if (!in) v[i] = make_float2(0.f, 0.f);
+          }
+          tb::split3_pk(v[0].y, v[1].x, p[h][0][0], p[h][0][1], p[h][0][2]);
+          tb::split3_pk(v[1].y, v[2].x, p[h][1][0], p[h][1][1], p[h][1][2]);
+          tb::split3_pk(v[2].y, v[3].x, p[h][2][0], p[h][2][1], p[h][2][2]);
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            p[h][3][q] = __builtin_amdgcn_alignbit(p[h][1][q], p[h][0][q], 16);
+            p[h][4][q] = __builtin_amdgcn_alignbit(p[h][2][q], p[h][1][q], 16);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          bf[0][q] = __builtin_bit_cast(tb::bf16x8, u32x4{p[0][0][q], p[0][1][q], p[1][0][q], p[1][1][q]});
+          bf[1][q] = __builtin_bit_cast(tb::bf16x8, u32x4{p[0][3][q], p[0][4][q], p[1][3][q], p[1][4][q]});
+          bf[2][q] = __builtin_bit_cast(tb::bf16x8, u32x4{p[0][1][q], p[0][2][q], p[1][1][q], p[1][2][q]});
+        }
+      }
+#pragma unroll
+      for (int tz = 0; tz < 3; ++tz) {
+        const float2* src = reinterpret_cast<const float2*>(gp[tz] + 4 * ga);
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float2 t = src[i];
+          v[2 * i] = t.x;
+          v[2 * i + 1] = t.y;
+        }
+        tb::bf16x8 af[3];
+        tb::split3(v, af[0], af[1], af[2]);
+#pragma unroll
+        for (int tx = 0; tx < 3; ++tx) tb::mfma_split6(af, bf[tx], hi[tz * 3 + tx], lo[tz * 3 + tx]);
+      }
+    }
+  }
+  // waves 6..11 (steps 2, 3 mod 4) hand their sums to waves 0..5, which fill the two slots of the image
+  float* red = smem;  // [27][2][4 rr][64 lanes]
+  const int rs = sp & 1;
+  __syncthreads();  // the ring is free
+  if (sp >= 2) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        red[((((j / 3) * 9 + ty * 3 + j % 3) * 2 + rs) * 4 + rr) * 64 + lane] = hi[j][rr] + lo[j][rr];
+  }
+  __syncthreads();
+  if (sp < 2) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        hi[j][rr] = (hi[j][rr] + lo[j][rr]) + red[((((j / 3) * 9 + ty * 3 + j % 3) * 2 + rs) * 4 + rr) * 64 + lane];
+  }
+  __syncthreads();
+  if (sp < 2) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        red[((((j / 3) * 9 + ty * 3 + j % 3) * 2 + rs) * 4 + rr) * 64 + lane] = hi[j][rr];
+  }
+  __syncthreads();
+  float* pt = a.part ? a.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (16 * 16 * 27) : nullptr;
+  for (int e = tid; e < 27 * 4 * 64; e += NT) {  // e = (j, rr, lane)
+    const int ln = e & 63, rr = (e >> 6) & 3, j = e >> 8;
+    const int m = (ln >> 4) * 4 + rr, c = ln & 15;
+    const float v = red[((j * 2 + 0) * 4 + rr) * 64 + ln] + red[((j * 2 + 1) * 4 + rr) * 64 + ln];
+    if (pt) {
+      pt[(m * 16 + c) * 27 + j] = v;  // the whole tile (zeros past mv, cv)
     } else if (m < mv && c < cv) {
       atomicAdd(&a.dW[((int64_t)(m0 + m) * a.Cc + (c0 + c)) * 27 + j], v);
     }
@@ -1312,9 +1558,26 @@ int zm_setup(ZmArgs& a, size_t& lds, dim3& grid, int N, int M, int Cc, int D, in
   return TB_OK;
 }
 
+// The split-bf16 kernel (k_conv3d_wgrad_zm_split, 12 waves) runs under the same record, grid and LDS size
+// where it was measured faster (profiles/r20/README.md; conv.wgrad with cold caches, median of three runs,
+// f32 kernel -> split kernel):
+//   16 -> 16 at 2 x 120 x 120 x 80   338.3 -> 282.2 us      32 -> 32 at 2 x 60 x 60 x 40   171.8 -> 136.8 us
+//   C = 16 and 32 at 2 x 32 x 32 x W, W = 8, 16, 24, 28, 32, 40, 48, 64, 80: 0.94x .. 0.77x of the f32 kernel's time
+//   W = 12: C = 16 25.8 -> 25.1, C = 32 37.5 -> 38.1 us; W = 20: 29.4 -> 29.6, 44.4 -> 44.4, and 64 -> 64 at
+//   2 x 30 x 30 x 20 100.4 -> 105.5 us: rows of 1.5 and 2.5 steps of 32 positions (a third / a fifth of the
+//   lanes idle in the last step, 6 / 9 of the 12 waves at work) stay on the f32 kernel
+// Other widths take the nearer measured neighbour's decision.  YB = 2 (never planned for W <= 80) has no
+// split instantiation.
+bool zm_split(const ZmArgs& a) { return a.YB == 4 && a.W != 12 && a.W != 20; }
+
 // 8 waves per block (one block per CU: two waves per SIMD; 4-wave blocks two per CU measured slower,
 // 4-wave blocks one per CU 7 -- 20 us slower per call)
 int launch_zm(const ZmArgs& a, size_t lds, dim3 grid, hipStream_t st) {
+  if (zm_split(a)) {
+    auto kern = a.W % 8 == 0 ? (a.W > 40 ? k_conv3d_wgrad_zm_split<4, 20, true> : k_conv3d_wgrad_zm_split<4, 10, true>)
+                             : (a.W > 40 ? k_conv3d_wgrad_zm_split<4, 20, false> : k_conv3d_wgrad_zm_split<4, 10, false>);
+    return tb::launch_lds(kern, grid, dim3(768), lds, st, a);
+  }
   auto kern = a.W > 40 ? (a.YB == 4 ? k_conv3d_wgrad_zm<4, 20, 8> : k_conv3d_wgrad_zm<2, 20, 8>)
                        : (a.YB == 4 ? k_conv3d_wgrad_zm<4, 10, 8> : k_conv3d_wgrad_zm<2, 10, 8>);
   return tb::launch_lds(kern, grid, dim3(512), lds, st, a);

@@ -21,6 +21,10 @@ a = ap.parse_args()
 rows = list(csv.DictReader(open(a.trace)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 starts = [int(r["Start_Timestamp"]) for r in rows if a.marker in r["Kernel_Name"]]
+if len(starts) < a.steps * a.per_step:
+    names = sorted({re.sub(r"\(.*", "", r["Kernel_Name"].replace("void ", ""))[:90] for r in rows})
+    raise SystemExit(f"marker {a.marker!r}: {len(starts)} launches in {a.trace}, {a.steps * a.per_step} needed "
+                     f"(--steps x --per-step); the trace's {len(names)} distinct kernel names:\n  " + "\n  ".join(names))
 t0 = starts[-a.steps * a.per_step]
 agg = collections.defaultdict(lambda: [0, 0])
 t_end = 0

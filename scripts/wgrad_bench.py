@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Time tb_conv3d_wgrad_f32 and tb_channel_sum_f32 on the U-Net's C3 layer shapes (HIP events,
-median of 10); prints one line per (layer, variant).  Diagnostic for tuning, not the headline."""
+median of 10); prints one line per (layer, variant).  Diagnostic for tuning, not the headline.
+--flush fills 1 GiB between calls (cold caches, as in the train step); --zm times only the stride-1
+z-marching layers; --sweep adds a row-width sweep at C = 16 and 32 (D = 32, H = 32, N = 2)."""
+import argparse
 import os
 import sys
 
@@ -21,29 +24,49 @@ LAYERS = [  # name, G shape, X shape, stride (G = grad_out / low-res x, X = inpu
 ]
 
 
-def timeit(fn, n=10):
+FLUSH = None
+
+
+def timeit(fn, n=10, warm=2):
     ts = []
-    for _ in range(n + 2):
+    for _ in range(n + warm):
+        if FLUSH is not None:
+            FLUSH.fill_(1.0)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         fn()
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    ts = sorted(ts[2:])
+    ts = sorted(ts[warm:])
     return ts[len(ts) // 2]
 
 
 def main():
+    global FLUSH
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--flush", action="store_true")
+    ap.add_argument("--zm", action="store_true")
+    ap.add_argument("--sweep", action="store_true")
+    a = ap.parse_args()
     torch.manual_seed(0)
     tag = os.environ.get("TAG", "")
-    for name, gs, xs, s in LAYERS:
+    if a.flush:
+        FLUSH = torch.empty(1 << 28, device="cuda")
+    warm = 3 if a.flush else 2
+    layers = [l for l in LAYERS if not a.zm or (l[3] == 1 and l[1][1] >= 8)]
+    if a.sweep:
+        layers += [(f"sweep C={c} W={w}", (2, c, 32, 32, w), (2, c, 32, 32, w), 1)
+                   for c in (16, 32) for w in (8, 12, 16, 20, 24, 28, 32, 40, 48, 64, 80)]
+    for name, gs, xs, s in layers:
         G = torch.randn(gs, device="cuda")
         X = torch.randn(xs, device="cuda")
         w_shape = (gs[1], xs[1], 3, 3, 3)
-        ms = timeit(lambda: C.wgrad(G, X, w_shape, s, 1))
+        ms = timeit(lambda: C.wgrad(G, X, w_shape, s, 1), warm=warm)
         flop = 2.0 * gs[1] * xs[1] * 27 * gs[0] * gs[2] * gs[3] * gs[4]
         print(f"{tag} wgrad {name:22s} {ms * 1e3:9.1f} us  {flop / ms / 1e9:7.1f} TF/s", flush=True)
+    if a.zm:
+        return
     g = torch.randn((2, 16, 120, 120, 80), device="cuda")
     ms = timeit(lambda: C.channel_sum(g))
     ms2 = timeit(lambda: g.sum((0, 2, 3, 4)))
