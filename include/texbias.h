@@ -404,6 +404,12 @@ int tb_convT3d_mfma64_f32(const float* x, const float* W, const float* bias, flo
  * that layer's input gradient (dX = conv_transpose3d(dY, W)). */
 int tb_convT3d_mfma_f32(const float* x, const float* W, const float* bias, float* y, int N, int Cin, int Di, int Hi,
                         int Wi, void* stream);
+/* ... with `add` (y's layout within a sample, or NULL) summed into the store; y's samples y_sn floats apart and
+ * add's add_sn (0: contiguous; otherwise each a channel slice of a wider tensor, even, y and add 8-B aligned).
+ * Cin = 64 rows of 32 <= Wi <= 60 run in split precision on the bf16 matrix cores (k_convT_split), the rest on
+ * the f32 matrix cores; both entries above pick the same way. */
+int tb_convT3d_mfma_add_f32(const float* x, const float* W, const float* bias, const float* add, int64_t add_sn,
+                            float* y, int64_t y_sn, int N, int Cin, int Di, int Hi, int Wi, void* stream);
 
 /* Conv3d(C -> C, 3, stride 1, padding 1) forward for C = 32 or 64 on the f32 matrix cores (the input
  * channels split over the block's waves, partial tiles summed in LDS): x [N][C][D][H][W] -> y,

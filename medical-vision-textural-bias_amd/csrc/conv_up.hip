@@ -1002,10 +1002,12 @@ struct T64Args {
   const float* x;     // [N][64][Di][Hi][Wi]
   const float* W;     // [64 c][16 m][27]
   const float* bias;  // [16] or null
-  float* y;           // [N][16][2 Di][2 Hi][2 Wi]
+  const float* add;   // summed into y (y's layout within a sample, samples addsn floats apart), or null
+  float* y;           // [N][16][2 Di][2 Hi][2 Wi], samples ysn floats apart
   int Di, Hi, Wi;
   int ZS, zlen, nyb;
   int PX, RX;         // staged row pitch (data at columns 0 .. Wi - 1, zeros after), channel pitch (16 mod 32)
+  int64_t ysn, addsn;
 };
 
 // G channel groups (Cin = 16 G): with G = 2 the waves (g, h) also split the position tiles (h = tile parity).
@@ -1076,7 +1078,10 @@ __global__ __launch_bounds__(256) void k_convT_mfma64(T64Args a) {
   __syncthreads();
   const int npos = YB * Wi, ntile = (npos + 15) / 16;
   const int64_t oplane = 4 * plane, orow = 2 * Wi;
-  float* yb0 = a.y + (int64_t)n * 16 * (2 * Di) * oplane;
+  float* yb0 = a.y + (int64_t)n * a.ysn;
+  // `add` (a wave-uniform branch: this kernel is the fall-back of k_convT_split, which fetches its add values
+  // ahead of the MFMAs; here they are read at the head of the sum phase, ahead of the partials' LDS reads)
+  const float* ab0 = a.add ? a.add + (int64_t)n * a.addsn : nullptr;
   // (tile phase h', parity pair (pz, py, 0 / 1)) combos over the waves: the G groups' partials summed
   auto sums = [&](int z, int t0, int pb) {
     const float* pr = part + pb * 4 * 8 * 256;
@@ -1084,6 +1089,14 @@ __global__ __launch_bounds__(256) void k_convT_mfma64(T64Args a) {
       const int hq = k >> 2, pz = (k >> 1) & 1, py = k & 1, q0 = pz * 4 + py * 2;
       const int pq = 16 * (t0 + hq) + li, yq = pq / Wi, xq = pq - yq * Wi;
       const bool okp = t0 + hq < ntile && pq < npos && y0 + yq < Hi;
+      float2 av[4];
+      if (ab0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          av[r] = okp ? *reinterpret_cast<const float2*>(ab0 + ((int64_t)(4 * ks + r) * (2 * Di) + 2 * z + pz) * oplane +
+                                                         (int64_t)(2 * (y0 + yq) + py) * orow + 2 * xq)
+                      : make_float2(0.f, 0.f);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = 4 * ks + r, e = m * 16 + li;
@@ -1093,6 +1106,7 @@ __global__ __launch_bounds__(256) void k_convT_mfma64(T64Args a) {
           v0 += pr[((hq * G + v) * 8 + q0) * 256 + e];
           v1 += pr[((hq * G + v) * 8 + q0 + 1) * 256 + e];
         }
+        if (ab0) v0 += av[r].x, v1 += av[r].y;
         if (okp)
           *reinterpret_cast<float2*>(yb0 + ((int64_t)m * (2 * Di) + 2 * z + pz) * oplane +
                                      (int64_t)(2 * (y0 + yq) + py) * orow + 2 * xq) = make_float2(v0, v1);
@@ -1145,6 +1159,241 @@ __global__ __launch_bounds__(256) void k_convT_mfma64(T64Args a) {
 }
 }  // namespace
 
+// ------------------------------------------------- the same product in split precision on the bf16 matrix cores
+// k_convT_mfma64's sub-pixel product (Cin = 64) on v_mfma_f32_16x16x32_bf16 (split_bf16.h), staged as
+// k_conv_mfma_split stages.  A 32-k step is two taps of ONE parity class x the 16 channels of one channel
+// group; the classes (pz py px) own 1, 2, 2, 4, 2, 4, 4, 8 taps (tap_of(kind = 2) of conv_gemm.hip), the
+// single-tap class 0 is padded with a zero-weight tap: 14 steps per group.  8 waves: wave w takes channel group
+// w & 3 and one half of the steps, w >> 2 -- classes 7, 3, 0 (4 + 2 + 1 steps) or 5, 6, 1, 2, 4 (2 + 2 + 1 + 1 + 1)
+// -- so it holds 7 steps x 3 parts = 84 A registers (split once at start-up), not 168, the two waves of a SIMD
+// share every B position, and one 16-position tile at a time is in flight: its partials [group][class][lane]
+// float4 are 32 KiB, double-buffered 64 KiB, one barrier per tile.  Each class runs its own (hi, lo)
+// accumulator pair; hi + lo is added once and goes to the partials.  After the barrier wave w sums classes
+// (w & 3) * 2 + {0, 1} (px = 0, 1) for rows 4 g4 + 2 (w >> 2) + {0, 1}: the four groups in order, then the bias,
+// then `add` (fetched ahead of the tile's MFMAs), then one float2 store per row.  No atomics.
+// LDS: a 2-slot plane ring (planes z, z + 1) of bf16 part images [slot][part][group][row 0..YB][position
+// 0..Wi][16 ch], position = x, position Wi the zero right neighbour: Wi + 1 positions are 1 mod 4, a row pitch
+// of 8 dwords mod 32 as k_conv_mfma_split's Wi + 5, and at Wi = 40, YB = 2 the ring is 94 464 B, with the
+// partials 160 000 B of the 163 840.  A staging task (channel quad, row, x quad, group) loads four float4 a
+// step ahead, nothing conditional on them, and splits them at the LDS store, rows and planes outside the volume
+// masked to zero there; threads past the last task repeat an earlier one (the same values to the same place).
+namespace {
+struct TSArgs {
+  const float* x;     // [N][64][Di][Hi][Wi]
+  const float* W;     // [64 c][16 m][27]
+  const float* bias;  // [16] or null
+  const float* add;   // summed into y (y's layout within a sample, samples addsn floats apart), or null
+  float* y;           // [N][16][2 Di][2 Hi][2 Wi], samples ysn floats apart
+  int Di, Hi, Wi, YB;
+  int ZS, zlen, nyb;
+  int ntile;          // position tiles per step: ceil(YB Wi / 16)
+  int64_t ysn, addsn;
+};
+
+struct CtTap {
+  int t, dz, dy, dx;  // weight tap, input offset
+};
+// tap j of parity class cls: per axis parity 0 takes tap 1 at offset 0; parity 1 takes i = 0 -> tap 2 at
+// offset 0, i = 1 -> tap 0 at offset +1; x fastest (tap_of(kind = 2))
+constexpr CtTap ct_tap(int cls, int j) {
+  const int pz = (cls >> 2) & 1, py = (cls >> 1) & 1, px = cls & 1;
+  const int nx = 1 + px, ny = 1 + py;
+  const int ix = j % nx, iy = (j / nx) % ny, iz = j / (nx * ny);
+  return CtTap{(pz ? (iz ? 0 : 2) : 1) * 9 + (py ? (iy ? 0 : 2) : 1) * 3 + (px ? (ix ? 0 : 2) : 1), pz ? iz : 0,
+               py ? iy : 0, px ? ix : 0};
+}
+constexpr int ct_ntap(int cls) { return (1 + ((cls >> 2) & 1)) * (1 + ((cls >> 1) & 1)) * (1 + (cls & 1)); }
+// step s (0 .. 6) of a half: its class, and which pair of the class's taps
+constexpr int ct_cls(int half, int s) {
+  return half == 0 ? (s < 4 ? 7 : s < 6 ? 3 : 0) : (s < 2 ? 5 : s < 4 ? 6 : s == 4 ? 1 : s == 5 ? 2 : 4);
+}
+constexpr int ct_pair(int half, int s) { return half == 0 ? (s < 4 ? s : s < 6 ? s - 4 : 0) : (s < 4 ? (s & 1) : 0); }
+// the two taps of step s; a class of one tap repeats it (its second tap's weights are zero)
+constexpr CtTap ct_step_tap(int half, int s, int hi) {
+  const int cls = ct_cls(half, s), e = 2 * ct_pair(half, s) + hi;
+  return ct_tap(cls, e < ct_ntap(cls) ? e : ct_ntap(cls) - 1);
+}
+constexpr bool ct_step_pad(int half, int s, int hi) { return 2 * ct_pair(half, s) + hi >= ct_ntap(ct_cls(half, s)); }
+
+// One tile's seven steps of half HALF: step s + 1's B fragments read ahead of step s's six MFMAs; a class's
+// hi + lo written to its partial tile when its last step is done.
+template <int HALF>
+__device__ __forceinline__ void ct_mma(const tb::bf16x8 (&af)[7][3], const char* rb, int sb0, int sb1, int RPB, int SPL,
+                                       int hv, char* pw) {
+  using tb::bf16x8;
+  bf16x8 bq[2][3];
+  auto ldb = [&](int s, bf16x8 (&bf)[3]) {  // read in the order the products take them: parts 1, 2, 0
+    const CtTap t0 = ct_step_tap(HALF, s, 0), t1 = ct_step_tap(HALF, s, 1);
+    const int c0 = (t0.dz ? sb1 : sb0) + t0.dy * RPB + t0.dx * 32;
+    const int c1 = (t1.dz ? sb1 : sb0) + t1.dy * RPB + t1.dx * 32;
+    const int o = hv ? c1 : c0;
+    bf[1] = *reinterpret_cast<const bf16x8*>(rb + o + SPL);
+    bf[2] = *reinterpret_cast<const bf16x8*>(rb + o + 2 * SPL);
+    bf[0] = *reinterpret_cast<const bf16x8*>(rb + o);
+  };
+  tb::f32x4s c = {0.f, 0.f, 0.f, 0.f}, cs = c;  // leading / small products of the class in flight
+  ldb(0, bq[0]);
+#pragma unroll
+  for (int s = 0; s < 7; ++s) {
+    if (s + 1 < 7) ldb(s + 1, bq[(s + 1) & 1]);
+    tb::mfma_split6(af[s], bq[s & 1], c, cs);
+    if (s == 6 || ct_cls(HALF, s + 1) != ct_cls(HALF, s)) {
+      c += cs;
+      *reinterpret_cast<tb::f32x4s*>(pw + ct_cls(HALF, s) * 1024) = c;
+      c = tb::f32x4s{0.f, 0.f, 0.f, 0.f}, cs = c;
+    }
+  }
+  // schedule: step s + 1's three reads, then step s's six MFMAs
+  __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+  }
+  __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(512) void k_convT_split(TSArgs a) {
+  using tb::bf16x8;
+  constexpr int G = 4, NTH = 512;
+  extern __shared__ __attribute__((aligned(16))) char ringt[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = w & 3, half = w >> 2;
+  const int Di = a.Di, Hi = a.Hi, Wi = a.Wi, YB = a.YB, NR = YB + 1;
+  const int RPB = (Wi + 1) * 32, GPB = NR * RPB, SPL = G * GPB, SLOT = 3 * SPL;  // bytes: row, group, part, slot
+  char* part = ringt + 2 * SLOT;  // [2 buf][4 groups][8 classes][64 lanes] float4
+  for (int i = tid; i < 2 * SLOT / 16; i += NTH) reinterpret_cast<uint4*>(ringt)[i] = make_uint4(0, 0, 0, 0);
+  int b = (int)blockIdx.x;
+  const int zs = b % a.ZS;
+  b /= a.ZS;
+  const int yb = b % a.nyb, n = b / a.nyb;
+  const int y0 = yb * YB;
+  const int z0 = zs * a.zlen, z1 = min(Di, z0 + a.zlen);
+  // A: lane (m = l & 15, g4 = l >> 4), step s: tap hi = g4 >> 1 of the step's two, channels 16 grp + 8 (g4 & 1) + j
+  const int li = lane & 15, g4 = lane >> 4, hi = g4 >> 1;
+  bf16x8 af[7][3];
+  {
+    const float* wl = a.W + ((16 * grp + 8 * (g4 & 1)) * 16 + li) * 27;
+#pragma unroll
+    for (int s = 0; s < 7; ++s) {
+      const int t = half ? (hi ? ct_step_tap(1, s, 1).t : ct_step_tap(1, s, 0).t)
+                         : (hi ? ct_step_tap(0, s, 1).t : ct_step_tap(0, s, 0).t);
+      const bool pad = hi && (half ? ct_step_pad(1, s, 1) : ct_step_pad(0, s, 1));
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = wl[j * 16 * 27 + t];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = pad ? 0.f : v[j];  // the tap that does not exist: zero weights
+      tb::split3(v, af[s][0], af[s][1], af[s][2]);
+    }
+  }
+  const int64_t plane = (int64_t)Hi * Wi, cstride = (int64_t)Di * plane;
+  const char* xb = reinterpret_cast<const char*>(a.x + (int64_t)n * 16 * G * cstride);
+  // this thread's staging task (channel quad fastest, then row, x quad, group); threads past the last task
+  // repeat task tid mod ntask
+  const int W4 = Wi >> 2, ntask = 4 * NR * W4 * G;
+  const int tk = tid < ntask ? tid : tid % ntask;
+  const int cq = tk & 3, rr = (tk >> 2) % NR, r2 = (tk >> 2) / NR, q4 = r2 % W4, sg = r2 / W4;
+  const int lof = sg * GPB + rr * RPB + 4 * q4 * 32 + cq * 8;
+  const int yi = y0 + rr;
+  const bool rowok = yi < Hi;
+  // per-lane byte offsets (32 bits: the host keeps a sample below 2 GiB) on wave-uniform bases
+  const unsigned chb = (unsigned)(4 * cstride);
+  const unsigned gof = rowok ? (unsigned)(16 * sg + 4 * cq) * chb + 4u * (unsigned)(yi * Wi + 4 * q4) : 0u;
+  float4 rg[4];
+  auto load = [&](int zi) {  // nothing conditional; zeroed by the mask at the store
+    const char* src = xb + (int64_t)(zi >= Di ? Di - 1 : zi) * plane * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) rg[c] = *reinterpret_cast<const float4*>(src + c * chb + gof);
+  };
+  auto store = [&](int zi) {
+    char* d = ringt + (zi & 1) * SLOT + lof;
+    const unsigned m = 0u - (unsigned)(rowok && zi < Di);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        v[c] = __uint_as_float(__float_as_uint(e == 0 ? rg[c].x : e == 1 ? rg[c].y : e == 2 ? rg[c].z : rg[c].w) & m);
+      unsigned p[3][2];
+      tb::split3_pk(v[0], v[1], p[0][0], p[1][0], p[2][0]);
+      tb::split3_pk(v[2], v[3], p[0][1], p[1][1], p[2][1]);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) *reinterpret_cast<uint2*>(d + s * SPL + e * 32) = make_uint2(p[s][0], p[s][1]);
+    }
+  };
+  // the sum phase's share of this wave: classes q0, q0 + 1 (px = 0, 1), rows m0 + {0, 1}
+  const int pzs = (w >> 1) & 1, pys = w & 1, q0 = pzs * 4 + pys * 2, rh = w >> 2;
+  const int m0 = 4 * g4 + 2 * rh;
+  const float bm[2] = {a.bias ? a.bias[m0] : 0.f, a.bias ? a.bias[m0 + 1] : 0.f};
+  __syncthreads();
+  load(z0);
+  store(z0);
+  load(z0 + 1);
+  store(z0 + 1);
+  // every start-up load (weights, bias, the first planes) retired here: no vmcnt(0) ahead of a step's MFMAs
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __syncthreads();
+  const int npos = YB * Wi, ntile = a.ntile;
+  const int64_t oplane = 4 * plane, orow = 2 * Wi, och = 2 * Di * oplane;
+  float* yb0 = a.y + (int64_t)n * a.ysn;
+  const float* ab0 = ADD ? a.add + (int64_t)n * a.addsn : nullptr;
+  const int lb = grp * GPB + 16 * (g4 & 1);  // B lane base: the wave's group, channel half g4 & 1
+  int buf = 0;
+  // step z: fetch plane z + 2 | per tile: its `add` values fetched, 42 MFMAs, hi + lo per class to the
+  // partials, barrier, the tile's sums and stores (they read the buffer the next tile does not write) | barrier
+  for (int z = z0; z < z1; ++z) {
+    load(z + 2);
+    int hv = hi;  // opaque: the per-step B offsets it selects are recomputed, not kept in registers
+    asm volatile("" : "+v"(hv));
+    const int sb0 = (z & 1) * SLOT, sb1 = ((z + 1) & 1) * SLOT;  // byte offsets of planes z, z + 1
+    // the step's last tile (LAST) splits plane z + 2 over plane z's slot right after its barrier (no wave reads
+    // that slot any more) and before its own output stores: the wait for the plane's loads then has only
+    // stores a tile old behind it, and stands on no skippable path
+    auto tile = [&](int t, auto LAST) {
+      const int p = 16 * t + li, pc = p < npos ? p : npos - 1;  // past the last position: the last one's values
+      const int yy = pc / Wi, xx = pc - yy * Wi;
+      const bool ok = p < npos && y0 + yy < Hi;
+      // C: column = position li, rows m0, m0 + 1 of classes q0, q0 + 1: one float2 (px = 0, 1) per row
+      const int64_t oo = ((int64_t)m0 * (2 * Di) + 2 * z + pzs) * oplane +
+                         (int64_t)(2 * min(y0 + yy, Hi - 1) + pys) * orow + 2 * xx;
+      float2 av[2];
+      if constexpr (ADD) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) av[r] = *reinterpret_cast<const float2*>(ab0 + oo + r * och);
+      }
+      const char* rb = ringt + lb + yy * RPB + xx * 32;
+      char* pw = part + (buf * 4 + grp) * 8192 + lane * 16;
+      if (half == 0)
+        ct_mma<0>(af, rb, sb0, sb1, RPB, SPL, hv, pw);
+      else
+        ct_mma<1>(af, rb, sb0, sb1, RPB, SPL, hv, pw);
+      __syncthreads();
+      if constexpr (decltype(LAST)::value) store(z + 2);  // (after the last step a dead slot)
+      const char* pr = part + (buf * 32 + q0) * 1024 + lane * 16 + 8 * rh;
+      tb::f32x2s v0 = *reinterpret_cast<const tb::f32x2s*>(pr), v1 = *reinterpret_cast<const tb::f32x2s*>(pr + 1024);
+#pragma unroll
+      for (int gg = 1; gg < G; ++gg) {  // the groups in order
+        v0 += *reinterpret_cast<const tb::f32x2s*>(pr + gg * 8192);
+        v1 += *reinterpret_cast<const tb::f32x2s*>(pr + gg * 8192 + 1024);
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        float2 o = make_float2(v0[r] + bm[r], v1[r] + bm[r]);
+        if constexpr (ADD) o.x += av[r].x, o.y += av[r].y;  // outside the branch: waited for on every path
+        if (ok) *reinterpret_cast<float2*>(yb0 + oo + r * och) = o;
+      }
+      buf ^= 1;
+    };
+    for (int t = 0; t + 1 < ntile; ++t) tile(t, std::false_type{});
+    tile(ntile - 1, std::true_type{});
+    __syncthreads();
+  }
+}
+}  // namespace
+
 // ConvTranspose3d(64 -> 16, 3, stride 2, padding 1, output_padding 1) forward:
 // x [N][64][Di][Hi][Wi] -> y [N][16][2Di][2Hi][2Wi]; weight [64][16][3][3][3] as the module holds it,
 // bias [16] or NULL; Wi % 4 == 0, Wi <= 64.  (csrc/conv_up.hip, k_convT_mfma64)
@@ -1153,36 +1402,100 @@ int tb_convT3d_mfma64_f32(const float* x, const float* W, const float* bias, flo
   return tb_convT3d_mfma_f32(x, W, bias, y, N, 64, Di, Hi, Wi, stream);
 }
 
-// ConvTranspose3d(Cin -> 16, 3, s2, p1, op1) forward for Cin = 32 or 64 (also the input gradient of
-// Conv3d(16 -> Cin, s2, p1) with that layer's weight); as tb_convT3d_mfma64_f32 otherwise.
-int tb_convT3d_mfma_f32(const float* x, const float* W, const float* bias, float* y, int N, int Cin, int Di, int Hi,
-                        int Wi, void* stream) {
+// The split kernel's plan for a shape, false where it does not serve it: Cin = 64 (the G = 2 form of Cin = 32 is
+// not built), a sample below 2 GiB (32-bit byte offsets), and the most rows per step, up to k_convT_mfma64's 2,
+// whose staging tasks fit the block's 512 threads and whose 2-slot ring and 64 KiB of partial tiles fit
+// 160 KiB: two rows up to Wi = 40, one up to Wi = 60; Wi = 64 has no plan.  Rows narrower than 32 stay on the
+// f32 kernel: with one or two position tiles per step the per-tile barrier and partial exchange are not hidden
+// (2 x 64 x 32 x 32 x W, caches flushed, f32 -> split us: W = 8 20.6 -> 31.1, 12 31.5 -> 36.3, 16 32.3 -> 36.5,
+// 20 43.6 -> 42.2, 24 44.2 -> 43.0, 32 55.7 -> 48.7, 40 68.7 -> 55.3, 48 79.4 -> 61.7; profiles/r21/README.md).
+static bool ct_plan(int Cin, int Di, int Hi, int Wi, TSArgs& s, size_t& lds) {
+  if (Cin != 64 || Wi < 32 || (int64_t)Cin * Di * Hi * Wi >= (1LL << 29)) return false;
+  for (int YB = std::min(2, Hi); YB >= 1; --YB) {
+    lds = (size_t)2 * 3 * 4 * (YB + 1) * (Wi + 1) * 32 + 65536;
+    if (4 * 4 * (YB + 1) * (Wi / 4) > 512 || lds > 163840) continue;
+    s.Di = Di, s.Hi = Hi, s.Wi = Wi, s.YB = YB;
+    s.ntile = (YB * Wi + 15) / 16;
+    s.nyb = (Hi + YB - 1) / YB;
+    return true;
+  }
+  return false;
+}
+
+// y (samples y_sn floats apart) = convT(x, W) + bias (+ add, samples add_sn floats apart); 0: contiguous
+static int convT_call(const float* x, const float* W, const float* bias, const float* add, int64_t add_sn, float* y,
+                      int64_t y_sn, int N, int Cin, int Di, int Hi, int Wi, void* stream) {
   if (!x || !W || !y || N < 1 || Di < 1 || Hi < 1 || Wi < 1) return TB_ERR_INVALID_ARG;
   if (Cin != 32 && Cin != 64) return TB_ERR_UNSUPPORTED_SIZE;
   if (Wi % 4 != 0 || Wi > 64 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 7) != 0)
     return TB_ERR_UNSUPPORTED_SIZE;
-  constexpr int YB = 2;
+  const int64_t ysz = (int64_t)16 * 8 * Di * Hi * Wi;  // floats of one output sample
+  if (y_sn == 0) y_sn = ysz;
+  if (add_sn == 0) add_sn = ysz;
+  // the float2 stores and `add` loads: 8-byte aligned samples
+  if (y_sn < ysz || (y_sn & 1) != 0 || (add && (add_sn < ysz || (add_sn & 1) != 0 || (reinterpret_cast<uintptr_t>(add) & 7) != 0)))
+    return TB_ERR_UNSUPPORTED_SIZE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // k_convT_split where its plan exists; k_convT_mfma64 otherwise
+  {
+    TSArgs s{};
+    size_t slds = 0;
+    if (ct_plan(Cin, Di, Hi, Wi, s, slds)) {
+      s.x = x, s.W = W, s.bias = bias, s.add = add, s.y = y, s.ysn = y_sn, s.addsn = add_sn;
+      s.zlen = tb::zseg(Di, N * s.nyb, 1, 1);  // 8 waves at 2 per SIMD: one block per CU
+      s.ZS = (Di + s.zlen - 1) / s.zlen;
+      return tb::launch_lds(add ? k_convT_split<true> : k_convT_split<false>, dim3((unsigned)(N * s.nyb * s.ZS)),
+                            dim3(512), slds, st, s);
+    }
+  }
+  // two input rows per step; one where the two-row ring does not fit (Cin = 64 past Wi = 52; of those only
+  // Wi = 64 comes here, the narrower ones have a split plan, so only that form is built)
   T64Args a{};
-  a.x = x, a.W = W, a.bias = bias, a.y = y, a.Di = Di, a.Hi = Hi, a.Wi = Wi;
+  a.x = x, a.W = W, a.bias = bias, a.add = add, a.y = y, a.Di = Di, a.Hi = Hi, a.Wi = Wi;
+  a.ysn = y_sn, a.addsn = add_sn;
   a.PX = Wi + 4;
-  a.RX = (YB + 1) * a.PX;
-  while ((a.RX & 31) != 16) ++a.RX;
+  int YB = 2;
+  size_t lds = 0;
+  for (; YB >= 1; --YB) {
+    a.RX = (YB + 1) * a.PX;
+    while ((a.RX & 31) != 16) ++a.RX;
+    lds = (size_t)4 * (2 * Cin * a.RX + 2 * 4 * 8 * 256);
+    if (lds <= 163840) break;
+  }
+  if (YB < 1) return TB_ERR_UNSUPPORTED_SIZE;
   a.nyb = (Hi + YB - 1) / YB;
-  const size_t lds = (size_t)4 * (2 * Cin * a.RX + 2 * 4 * 8 * 256);
-  if (lds > 163840) return TB_ERR_UNSUPPORTED_SIZE;
   a.zlen = tb::zseg(Di, N * a.nyb, 1, 1);
   a.ZS = (Di + a.zlen - 1) / a.zlen;
   const int nl = (Cin * (YB + 1) * (Wi / 4) + 255) / 256;
   void (*kern)(T64Args) = nullptr;
-  switch (nl) {
+  if (YB == 1) {
+    if (Cin == 64 && nl == 8) kern = k_convT_mfma64<4, 1, 8>;
+  } else {
+    switch (nl) {
 #define TB_NL(k) \
-  case k: kern = Cin == 64 ? k_convT_mfma64<4, YB, k> : k_convT_mfma64<2, YB, k>; break;
-    TB_NL(1) TB_NL(2) TB_NL(3) TB_NL(4) TB_NL(5) TB_NL(6) TB_NL(7) TB_NL(8) TB_NL(9) TB_NL(10) TB_NL(11) TB_NL(12)
+  case k: kern = Cin == 64 ? k_convT_mfma64<4, 2, k> : k_convT_mfma64<2, 2, k>; break;
+      TB_NL(1) TB_NL(2) TB_NL(3) TB_NL(4) TB_NL(5) TB_NL(6) TB_NL(7) TB_NL(8) TB_NL(9) TB_NL(10) TB_NL(11) TB_NL(12)
 #undef TB_NL
-    default: return TB_ERR_UNSUPPORTED_SIZE;
+      default: break;
+    }
   }
-  return tb::launch_lds(kern, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(256), lds,
-                        reinterpret_cast<hipStream_t>(stream), a);
+  if (!kern) return TB_ERR_UNSUPPORTED_SIZE;
+  return tb::launch_lds(kern, dim3((unsigned)(N * a.nyb * a.ZS)), dim3(256), lds, st, a);
+}
+
+// ConvTranspose3d(Cin -> 16, 3, s2, p1, op1) forward for Cin = 32 or 64 (also the input gradient of
+// Conv3d(16 -> Cin, s2, p1) with that layer's weight); as tb_convT3d_mfma64_f32 otherwise.
+int tb_convT3d_mfma_f32(const float* x, const float* W, const float* bias, float* y, int N, int Cin, int Di, int Hi,
+                        int Wi, void* stream) {
+  return convT_call(x, W, bias, nullptr, 0, y, 0, N, Cin, Di, Hi, Wi, stream);
+}
+
+// ... with `add` (or NULL) summed into the store, and y and add each a channel slice of a wider tensor where
+// their sample strides y_sn / add_sn (floats; 0: contiguous) say so: a stacked stride-2 unit's input gradient
+// plus the skip concatenation's share, written straight into the upstream unit's output-gradient buffer.
+int tb_convT3d_mfma_add_f32(const float* x, const float* W, const float* bias, const float* add, int64_t add_sn,
+                            float* y, int64_t y_sn, int N, int Cin, int Di, int Hi, int Wi, void* stream) {
+  return convT_call(x, W, bias, add, add_sn, y, y_sn, N, Cin, Di, Hi, Wi, stream);
 }
 
 // ------------------------------------------------- stride-1 3x3x3 conv, C -> C channels (C = 32, 64), on MFMA

@@ -295,6 +295,14 @@ FWD16_DX_ADD = True
 # the same for the 32 / 64-channel kernel: off (its add form holds 256 VGPRs, one wave per SIMD at 32 -> 32
 # instead of two, for a 6-19 us add pass)
 MFMA_DX_ADD = False
+# the stacked stride-2 unit's input gradient plus the skip concatenation's share, summed in the transposed-conv
+# kernel's store and written straight into the upstream unit's output-gradient buffer (texbias.unet), instead
+# of a separate add pass over three full-resolution tensors.  On: at C3 the call + add is 216.5 us separate, 171.5 us
+# in k_convT_split's store (caches flushed); in the step one elementwise launch and 0.069 ms of it go, the kernel
+# gains 25 us; the step's median moves by 0.040 ms, inside the spread of its runs (profiles/r21/README.md §2, §4, §5).
+# On k_convT_mfma64 (no split plan; its add values are read in the sum phase) the step measured 0.034 ms slower
+# with it than the parent's add pass: the C3 shape does not take that route.
+CONVT_DX_ADD = True
 
 
 def _gemm_geom_ok(x: torch.Tensor, w: torch.Tensor, stride, padding, transposed: bool, output_padding) -> bool:
@@ -424,16 +432,44 @@ def convT_fewout_applies(x: torch.Tensor, w: torch.Tensor, stride, padding, outp
         _s2_shape_ok(tuple(2 * n for n in x.shape[2:]))
 
 
-def convT_mfma(x: torch.Tensor, w: torch.Tensor, b) -> torch.Tensor:
+def _sample_stride(t: torch.Tensor, shape) -> int:
+    """The floats between samples of ``t`` when it is ``shape`` with every sample contiguous (a tensor of its
+    own, or a channel slice of a wider one), else -1."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t[0].is_contiguous():
+        return -1
+    return t.stride(0)
+
+
+def convT_mfma(x: torch.Tensor, w: torch.Tensor, b, add=None, out=None) -> torch.Tensor:
     """ConvTranspose3d(Cin -> 16, 3, stride 2, padding 1, output_padding 1), Cin = 32 or 64, forward on the
-    f32 matrix cores (tb_convT3d_mfma_f32; w [Cin, 16, 3, 3, 3] as the module holds it)."""
+    matrix cores (w [Cin, 16, 3, 3, 3] as the module holds it): Cin = 64 in split precision on the bf16 cores
+    where the kernel has a plan (k_convT_split), else on the f32 cores (k_convT_mfma64).  ``add`` (the output's
+    shape) is summed into the kernel's store and ``out`` receives the result; each may be a channel slice of a
+    wider tensor, read / written in place (tb_convT3d_mfma_add_f32)."""
     x = x.contiguous()
     N, Cin, D, H, W = x.shape
-    y = torch.empty((N, 16, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    shape = (N, 16, 2 * D, 2 * H, 2 * W)
+    if add is None and out is None:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().tb_convT3d_mfma_f32(x.data_ptr(), w.contiguous().data_ptr(),
+                                            b.data_ptr() if b is not None else None, y.data_ptr(), N, Cin, D, H, W,
+                                            _stream(x)), "tb_convT3d_mfma_f32")
+        return y
+    y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    ysn = _sample_stride(y, shape)
+    assert ysn > 0 and ysn % 2 == 0 and y.data_ptr() % 8 == 0, "out: the output's shape, samples contiguous"
+    asn = 0
+    if add is not None:
+        asn = _sample_stride(add, shape)
+        if asn <= 0 or asn % 2 or add.data_ptr() % 8:
+            add = add.contiguous()
+            asn = add.stride(0)
     with torch.cuda.device(x.device):
-        check(lib().tb_convT3d_mfma_f32(x.data_ptr(), w.contiguous().data_ptr(),
-                                        b.data_ptr() if b is not None else None, y.data_ptr(), N, Cin, D, H, W,
-                                        _stream(x)), "tb_convT3d_mfma_f32")
+        check(lib().tb_convT3d_mfma_add_f32(x.data_ptr(), w.contiguous().data_ptr(),
+                                            b.data_ptr() if b is not None else None,
+                                            add.data_ptr() if add is not None else None, asn, y.data_ptr(), ysn,
+                                            N, Cin, D, H, W, _stream(x)), "tb_convT3d_mfma_add_f32")
     return y
 
 
@@ -601,7 +637,7 @@ class Route:
     bias gradient -- chosen once from the shapes (the gates above), so that the layer's autograd function
     and the fused U-Net blocks (``texbias.unet``) share one dispatch.  Kinds: ``fwd16`` (k_conv3d_fwd16),
     ``mfma`` (k_conv3d_mfma_s1), ``fewin`` (k_conv_s2_fewin), ``small`` (k_conv3d_small_z), ``fewout``
-    (k_convT_fewout), ``convT64`` (k_convT_mfma64), ``gemm`` (k_conv_gemm), ``aten`` (MIOpen / CK)."""
+    (k_convT_fewout), ``convT64`` (k_convT_split / k_convT_mfma64), ``gemm`` (k_conv_gemm), ``aten`` (MIOpen / CK)."""
 
     __slots__ = ("kind", "dx", "stride", "padding", "output_padding", "transposed", "fast_w", "k", "wgg")
 
@@ -683,11 +719,17 @@ class Route:
         return F.conv3d(x, w, b, self.stride, self.padding)
 
     # -- input gradient (x only for its shape on the ATen path; ``add`` summed in, as in forward)
-    def input_grad(self, gy, x, w, add=None):
+    def input_grad(self, gy, x, w, add=None, out=None):
+        """``out`` (the ``convT64`` kernel only): where the result goes, a channel slice of a wider tensor."""
         k = self.dx
+        if out is not None:
+            assert k == "convT64"
+            return convT_mfma(gy if gy.data_ptr() % 16 == 0 else gy.clone(), w, None, add=add, out=out)
         if add is not None:  # (a strided add -- a channel slice of the skip concatenation's gradient -- is
             if k == "fwd16" and FWD16_DX_ADD:  # copied only for the kernels that need it contiguous)
                 return conv_fwd16_dgrad(gy, w, add)
+            if k == "convT64" and CONVT_DX_ADD:
+                return convT_mfma(gy if gy.data_ptr() % 16 == 0 else gy.clone(), w, None, add=add)
             if k == "mfma" and MFMA_DX_ADD:
                 return conv_mfma_dgrad(gy, w, add)
             if k == "small":

@@ -121,7 +121,7 @@ class _StackedUnitFn(torch.autograd.Function):
     a0 = ADN0(unit0), out = ADN1(conv1(a0)) + residual."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, wr, br, a0w, w1, b1, a1w, unit, eps, skip):
+    def forward(ctx, x, w0, b0, wr, br, a0w, w1, b1, a1w, unit, eps, skip, skip_in=None):
         c = w0.shape[0]
         w_st = _adjacent(w0, wr)
         if w_st is None:
@@ -143,6 +143,7 @@ class _StackedUnitFn(torch.autograd.Function):
         ctx.save_for_backward(x, w_st, a0w, w1, a1w, y2, a0, z1, m0, s0, m1, s1)
         ctx.cfg = (c, r_st, r1, b0 is not None, b1 is not None)
         ctx.skip = skip
+        ctx.skip_in = skip_in  # the hand-over dict of the stacked unit that made x, if one did
         return out
 
     @staticmethod
@@ -150,11 +151,17 @@ class _StackedUnitFn(torch.autograd.Function):
         x, w_st, a0w, w1, a1w, y2, a0, z1, m0, s0, m1, s1 = ctx.saved_tensors
         c, r_st, r1, has_b0, has_b1 = ctx.cfg
         n = ctx.needs_input_grad
-        dy2 = torch.empty_like(y2)
+        dy2, gd = ctx.skip.pop("dy2", None), ctx.skip.pop("gx", None)
         gs = ctx.skip.pop("g", None)
-        if gs is not None:  # the skip concatenation's share of this output's gradient, summed straight into
+        if dy2 is not None and gd is not None and gs is None and dy2.shape == y2.shape and \
+                g.data_ptr() == gd.data_ptr() and \
+                g.shape == gd.shape and g.stride() == gd.stride():
+            pass  # g is the downstream unit's input gradient + the skip share, already in dy2[:, c:]
+        elif gs is not None:  # the skip concatenation's share of this output's gradient, summed straight into
+            dy2 = torch.empty_like(y2)
             g = torch.add(g, gs, out=dy2[:, c:])  # the residual conv's half of the stacked output gradient
         else:
+            dy2 = torch.empty_like(y2)
             g = g.contiguous()
             dy2[:, c:].copy_(g)                               # the residual conv's output gradient
         # the residual conv's bias gradient (g summed over n and the voxels) out of the ADN's statistics sweep
@@ -164,10 +171,23 @@ class _StackedUnitFn(torch.autograd.Function):
         gw1 = r1.weight_grad(dz1, a0, w1) if n[6] else None
         _, dw0a, db0 = adn_backward(y2[:, :c], da0, m0, s0, a0w, need_w=n[5], need_bias=has_b0,
                                     dx_out=dy2[:, :c])
-        gx = r_st.input_grad(dy2, x, w_st) if n[0] else None
+        up = ctx.skip_in
+        gu = up.get("g") if up is not None else None
+        if n[0] and gu is not None and _conv.CONVT_DX_ADD and r_st.dx == "convT64" and gu.shape == x.shape:
+            # x is a stacked unit's output and its skip share gu is waiting: the kernel writes dX + gu into
+            # channels [cu, 2 cu) of that unit's stacked output-gradient buffer, which that unit's backward
+            # takes over when this very slice comes back to it as its output gradient (no add pass, no copy)
+            cu = x.shape[1]
+            buf = torch.empty((x.shape[0], 2 * cu) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+            gx = _alias(buf, cu, 2 * cu)
+            r_st.input_grad(dy2, x, w_st, add=gu, out=gx)
+            del up["g"]
+            up["dy2"], up["gx"] = buf, gx
+        else:
+            gx = r_st.input_grad(dy2, x, w_st) if n[0] else None
         gw_st = r_st.weight_grad(dy2, x, w_st) if (n[1] or n[3]) else None
         return (gx, gw_st[:c] if gw_st is not None else None, db0, gw_st[c:] if gw_st is not None else None, dbr,
-                dw0a, gw1, db1 if n[7] else None, da1, None, None, None)
+                dw0a, gw1, db1 if n[7] else None, da1, None, None, None, None)
 
 
 class ADN(nn.Sequential):
@@ -252,7 +272,8 @@ class ResidualUnit(nn.Module):
                     u0.adn.N.eps == u1.adn.N.eps and r.padding_mode == "zeros":
                 skip = {}
                 y = _StackedUnitFn.apply(x, u0.conv.weight, u0.conv.bias, r.weight, r.bias, u0.adn.A.weight,
-                                         u1.conv.weight, u1.conv.bias, u1.adn.A.weight, self, u0.adn.N.eps, skip)
+                                         u1.conv.weight, u1.conv.bias, u1.adn.A.weight, self, u0.adn.N.eps, skip,
+                                         getattr(x, "_tb_skip", None))
                 y._tb_skip = skip  # a skip concatenation of y hands its gradient share over (_SkipCatFn)
                 return y
         if isinstance(self.residual, nn.Identity) and len(units) == 1 and hasattr(units[0], "adn"):

@@ -5,14 +5,27 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "medical-vision-textural-bias_amd"), ROOT]
+import argparse  # noqa: E402
+import inspect  # noqa: E402
+
 import torch  # noqa: E402
 
 from texbias import conv as C  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--flush", action="store_true", help="write 1 GiB between timed calls (cold L2 / MALL)")
+ap.add_argument("--convt", action="store_true", help="only the ConvTranspose3d(64 -> 16) arms: forward, stacked "
+                "input gradient, and that gradient + the skip share into a channel slice")
+ap.add_argument("--sweep", action="store_true", help="--convt at 2 x 64 x 32 x 32 x W, W = 8 .. 64")
+args = ap.parse_args()
+_flush = torch.empty(1 << 28, device="cuda") if args.flush else None
 
 
 def timeit(fn, n=10):
     ts = []
     for _ in range(n + 3):
+        if _flush is not None:
+            _flush.add_(1.0)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         fn()
@@ -21,6 +34,36 @@ def timeit(fn, n=10):
         ts.append(a.elapsed_time(b))
     ts = sorted(ts[3:])
     return ts[len(ts) // 2] * 1e3
+
+
+def convt_arms(N, D, H, W, tag):
+    """FLOP per call: 2 x 64 x 16 x 27 x N D H W (every tap of every input position is one multiply-add)."""
+    fl = 2 * 64 * 16 * 27 * N * D * H * W
+    x = torch.randn((N, 64, D, H, W), device="cuda")
+    w = torch.randn((64, 16, 3, 3, 3), device="cuda")
+    t = timeit(lambda: C.convT_mfma(x, w, None))
+    print(f"convT 64->16 {tag} {D}x{H}x{W} fwd/dgrad        {t:8.1f} us  {fl / t / 1e6:6.1f} TF/s", flush=True)
+    # the level-1 skip share: dX + g into channels [16, 32) of the stacked output-gradient buffer
+    wide = torch.randn((N, 32, 2 * D, 2 * H, 2 * W), device="cuda")
+    buf = torch.empty_like(wide)
+    g = wide[:, :16]
+    if "out" in inspect.signature(C.convT_mfma).parameters:
+        t = timeit(lambda: C.convT_mfma(x, w, None, add=g, out=buf[:, 16:]))
+        print(f"convT 64->16 {tag} {D}x{H}x{W} dgrad + add in store {t:8.1f} us", flush=True)
+    t = timeit(lambda: torch.add(C.convT_mfma(x, w, None), g, out=buf[:, 16:]))
+    print(f"convT 64->16 {tag} {D}x{H}x{W} dgrad, separate add  {t:8.1f} us", flush=True)
+
+
+if args.convt or args.sweep:
+    if args.sweep:
+        for W in (8, 12, 16, 20, 24, 32, 40, 48, 64):
+            try:
+                convt_arms(2, 32, 32, W, "sweep")
+            except RuntimeError as e:  # a width the library refuses
+                print(f"convT 64->16 sweep 32x32x{W}: {e}", flush=True)
+    else:
+        convt_arms(2, 60, 60, 40, "C3")
+    sys.exit(0)
 
 
 x = torch.randn((2, 4, 240, 240, 160), device="cuda")
