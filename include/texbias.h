@@ -213,6 +213,52 @@ int tb_kspace_cmask_grad_f32(const tb_plan* plan, const float* x, const int64_t*
                              void* stream);
 
 /*
+ * Radial profiles in centred k-space: K >= 1 bins of width dr > 0 over the integer radius of an element
+ * s = (s_h, s_w, s_d) of the centred layout (that of TB_OP_MASK),
+ *   r2 = k_h^2 + k_w^2 + k_d^2,  k_a = s_a - floor(n_a / 2)   (disk_mask's metric; size-1 axes contribute 0)
+ *   u  = f32_sqrt((float)r2) * inv_dr,  inv_dr = (float)(1.0 / dr)   (one correctly rounded sqrt, one multiply)
+ *   TB_RADIAL_NEAREST  b = min((int)u, K-1), weight 1
+ *   TB_RADIAL_LINEAR   b0 = (int)u; b0 >= K-1: weight 1 on bin K-1; else t = u - (float)b0, weight 1-t on b0
+ *                      and t on b0+1
+ * The last bin is clamped: it collects (its value extends over) everything beyond (K-1) dr.  The weights
+ * w_k(s) of an element sum to 1, and r2 is invariant under f -> -f, so a radial mask is real and symmetric.
+ * With N = H W D, all sums in float64 and in a fixed order (no floating-point atomics; repeated calls agree
+ * bit for bit):
+ *   tb_radial_mask_f32           M[c][s]    = sum_k w_k(s) p[c][k]                      (expand)
+ *   tb_radial_bin_f32            q[c][k]    = sum_s w_k(s) A[c][s]                      (its adjoint)
+ *   tb_kspace_radial_power_f32   P[b][c][k] = sum_f w_k(f) |X_{b,c}(f)|^2 / N           (sum_k P = sum x^2)
+ *   tb_kspace_radial_grad_f32    dp[c][k]   = sum_f w_k(f) Re(X(f) conj(G(f))) / N      X = FFT(x), G = FFT(g),
+ *       summed over the B samples and, with Cp = 1, over the C channels: the gradient of
+ *       y = kspace_mask(x, expand(p)) with respect to p, equal to bin(tb_kspace_mask_grad_f32(x, g)).
+ *   x, xs, g, gs : as in tb_kspace_mask_grad_f32
+ *   P  : device float32 [B*C][K];   dp, p, q : device float32 [Cp][K] / [Cm][K];   M, A : device contiguous
+ *        float32 [Cp][H][W][D] / [Cm][H][W][D], centred layout.  Outputs are overwritten completely.
+ *   ws : device workspace of >= tb_radial_workspace_bytes(plan, B*C, K, with_g) bytes (with_g = 1 for the
+ *        gradient; tb_radial_bin_f32: tb_radial_workspace_bytes(plan, Cm, K, 0))
+ * Plans on the direct-DFT fallback, and every plan after tb_set_radial_fused(0) (a test switch, default 1),
+ * take the composed route: tb_kspace_mask_grad_f32 into the workspace (g = x, one sample at a time, for the
+ * power spectrum), then the dense bin reduction.  Every other plan runs pass A (twice for the gradient), the
+ * fused shell reduction and the ordered sum of its partials; no dM is written.  Nothing is allocated, no host
+ * sync, launches on `stream` only (graph-capturable).  TB_ERR_INVALID_ARG for a null pointer, B < 1, C < 1,
+ * K < 1 or K > TB_RADIAL_MAX_BINS, dr not finite or <= 0, mode outside {0, 1}, Cp or Cm neither 1 nor C
+ * (tb_radial_mask_f32 / tb_radial_bin_f32: Cp, Cm < 1); TB_ERR_WORKSPACE for a missing or short workspace;
+ * both before any launch.
+ */
+#define TB_RADIAL_NEAREST 0
+#define TB_RADIAL_LINEAR 1
+#define TB_RADIAL_MAX_BINS 2048 /* the K float64 sums of a workgroup live in LDS */
+size_t tb_radial_workspace_bytes(const tb_plan* plan, int bc, int K, int with_g);
+int tb_kspace_radial_power_f32(const tb_plan* plan, const float* x, const int64_t* xs, float* P, int K, double dr,
+                               int mode, void* ws, size_t ws_bytes, int B, int C, void* stream);
+int tb_kspace_radial_grad_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                              float* dp, int Cp, int K, double dr, int mode, void* ws, size_t ws_bytes, int B, int C,
+                              void* stream);
+int tb_radial_mask_f32(const tb_plan* plan, const float* p, int Cp, int K, double dr, int mode, float* M, void* stream);
+int tb_radial_bin_f32(const tb_plan* plan, const float* A, int Cm, int K, double dr, int mode, float* q, void* ws,
+                      size_t ws_bytes, void* stream);
+int tb_set_radial_fused(int enable);
+
+/*
  * The centred complex spectrum itself (Fourier.shift_fourier / inv_shift_fourier,
  * source_code/filters_and_operators.py:594-632), two linear maps, each the other's adjoint up to N = H W D:
  *   export  K = fftshift(fftn(x))             x real float32, K complex64

@@ -13,6 +13,7 @@
 
 #include "fft_core.h"
 #include "maskgrad.h"
+#include "radial.h"
 #include "sap_core.h"
 #include "spectrum.h"
 
@@ -75,6 +76,14 @@ template <int RS> hipError_t launch_kspace_maskgrad(const MaskGradArgs& a, dim3 
 // centred spectrum export / import (spectrum.h, kern_spectrum.hip): grid = (tiles of a.T columns, volumes)
 template <int RS> hipError_t launch_kspace_export(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_kspace_import(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
+
+// radial profiles (radial.h, kern_radial.hip).  launch_radial: grid = (units of a.tpg tiles, slots), self picks
+// k_radial_power; launch_radial_sum: the ordered sum of the partials; launch_radial_bin: grid = (units, a.Cm);
+// launch_radial_expand: one element-wise pass
+template <int RS> hipError_t launch_radial(const RadialArgs& a, bool self, dim3 grid, size_t lds, hipStream_t st);
+hipError_t launch_radial_sum(const RadialSumArgs& a, hipStream_t st);
+hipError_t launch_radial_bin(const RadialDenseArgs& a, int units, hipStream_t st);
+hipError_t launch_radial_expand(const RadialDenseArgs& a, hipStream_t st);
 
 // Compile-time slab plans (slab_ct.h, kern_slab_ct.hip): persistent passes A / C, grid from ncu.
 bool slab_ct_supported(int W, int D);

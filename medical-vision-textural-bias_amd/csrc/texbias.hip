@@ -1164,6 +1164,184 @@ int tb_kspace_cmask_grad_f32(const tb_plan* p, const float* x, const int64_t* xs
   return mask_grad_entry(p, x, xs, g, gs, static_cast<float*>(dM), Cm, ws, ws_bytes, B, C, stream, 1);
 }
 
+// ------------------------------------------------------------ radial profiles (radial.h)
+// Fused route: [S_x][S_g (gradient)][partials of the shell reduction].  Composed route (plans of
+// maskgrad_generic(), or tb_set_radial_fused(0)): [workspace of the mask gradient][dense dM][partials of
+// the dense bin reduction].  tb_radial_workspace_bytes covers both, so the switch may change between the
+// query and the call.
+static bool g_radial_fused = true;
+
+static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// dense bin reduction over N elements per channel: chunks of RB_CHUNK elements, at most 1024 units
+struct RadialBinGrid {
+  int cpu, units;
+};
+static RadialBinGrid radial_bin_grid(int64_t N) {
+  const int64_t chunks = (N + tb::RB_CHUNK - 1) / tb::RB_CHUNK;
+  RadialBinGrid g;
+  g.cpu = (int)((chunks + 1023) / 1024);
+  g.units = (int)((chunks + g.cpu - 1) / g.cpu);
+  return g;
+}
+// tiles per unit of the fused reduction: about eight workgroups per compute unit
+static int radial_tpg(const tb_plan* p, int ntiles, int slots) {
+  int64_t t = ((int64_t)ntiles * slots) / ((int64_t)p->ncu * 8);
+  if (t < 1) t = 1;
+  if (t > 16) t = 16;
+  return (int)t;
+}
+static size_t radial_spec_bytes(const tb_plan* p, int bc) {
+  return align256((size_t)bc * p->dev.H * p->dev.W * (p->dev.D / 2 + 1) * sizeof(cf));
+}
+static size_t radial_fused_bytes(const tb_plan* p, int bc, int K, int with_g) {
+  const int T = maskgrad_tile(p);
+  const int ntiles = (p->dev.W * (p->dev.D / 2 + 1) + T - 1) / T;
+  return (with_g ? 2 : 1) * radial_spec_bytes(p, bc) + (size_t)ntiles * bc * K * sizeof(double);
+}
+static size_t radial_composed_bytes(const tb_plan* p, int bc, int K) {
+  const int64_t N = (int64_t)p->dev.H * p->dev.W * p->dev.D;
+  return align256(tb_mask_grad_workspace_bytes(p, bc)) + align256((size_t)bc * N * sizeof(float)) +
+         (size_t)radial_bin_grid(N).units * bc * K * sizeof(double);
+}
+
+size_t tb_radial_workspace_bytes(const tb_plan* plan, int bc, int K, int with_g) {
+  if (!plan || bc < 1 || K < 1 || K > TB_RADIAL_MAX_BINS) return 0;
+  const size_t c = radial_composed_bytes(plan, bc, K);
+  if (maskgrad_generic(plan)) return c;
+  const size_t f = radial_fused_bytes(plan, bc, K, with_g);
+  return f > c ? f : c;
+}
+
+static bool radial_args_ok(int K, double dr, int mode) {
+  return K >= 1 && K <= TB_RADIAL_MAX_BINS && std::isfinite(dr) && dr > 0.0 &&
+         (mode == TB_RADIAL_NEAREST || mode == TB_RADIAL_LINEAR);
+}
+
+// q[Cm][K] = scale * bin(A[Cm][H][W][D]); part: radial_bin_grid(N).units * Cm * K doubles
+static int radial_bin(const tb_plan* p, const float* A, int Cm, int K, float inv_dr, int mode, float* q, double* part,
+                      hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D;
+  const RadialBinGrid bg = radial_bin_grid((int64_t)H * W * D);
+  Timer t(2, st, (double)Cm * H * W * D * 4.0, "k_radial_bin");
+  const tb::RadialDenseArgs da{H, W, D, Cm, K, mode, inv_dr, A, nullptr, part, tb::RB_CHUNK, bg.cpu};
+  TB_HIP(tb::launch_radial_bin(da, bg.units, st));
+  const tb::RadialSumArgs sa{part, q, bg.units, Cm * K, 1.0, 0};
+  TB_HIP(tb::launch_radial_sum(sa, st));
+  return TB_OK;
+}
+
+// g = nullptr: the power spectrum P[B*C][K]; else the profile gradient dp[Cp][K]
+template <int RA, int RB>
+static int kspace_radial(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                         float* out, int Cp, int K, float inv_dr, int mode, void* ws, int B, int C, hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  const int64_t N = (int64_t)H * W * D;
+  const bool self = g == nullptr;
+  if (maskgrad_generic(p) || !g_radial_fused) {
+    char* w = static_cast<char*>(ws);
+    float* dM = reinterpret_cast<float*>(w + align256(tb_mask_grad_workspace_bytes(p, B * C)));
+    double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(dM) + align256((size_t)B * C * N * sizeof(float)));
+    if (!self) {
+      const int rc = kspace_mask_grad<RA, RB>(p, x, xs, g, gs, dM, Cp, ws, B, C, st, 0);
+      if (rc) return rc;
+      return radial_bin(p, dM, Cp, K, inv_dr, mode, out, part, st);
+    }
+    for (int b = 0; b < B; ++b) {  // one sample at a time: no sum over samples
+      const float* xb = x + (int64_t)b * C * xs[0];
+      int rc = kspace_mask_grad<RA, RB>(p, xb, xs, xb, xs, dM, C, ws, 1, C, st, 0);
+      if (rc) return rc;
+      rc = radial_bin(p, dM, C, K, inv_dr, mode, out + (size_t)b * C * K, part, st);
+      if (rc) return rc;
+    }
+    return TB_OK;
+  }
+  const int T = maskgrad_tile(p);
+  const int ntiles = (W * Dh + T - 1) / T;
+  const size_t lds = (size_t)tb::radial_lds_cf(H, T, K) * sizeof(cf);
+  cf* Sx = static_cast<cf*>(ws);
+  cf* Sg = reinterpret_cast<cf*>(static_cast<char*>(ws) + radial_spec_bytes(p, B * C));
+  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + (self ? 1 : 2) * radial_spec_bytes(p, B * C));
+  const double scale = 1.0 / (double)N;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const double vox = (double)nb * C * N, spec = (double)nb * C * H * W * Dh * 8.0;
+    const int slots = self ? nb * C : Cp;
+    const int tpg = radial_tpg(p, ntiles, slots);
+    const int units = (ntiles + tpg - 1) / tpg;
+    {
+      Timer t(0, st, (self ? 1.0 : 2.0) * (vox * 4.0 + spec), use_ct_slab(p) ? "k_slab_fwd_ct16" : "k_slab_fwd");
+      int rc = launch_slab_fwd<RA>(p, x, xs, Sx, b0 * C, nb * C, st);
+      if (rc) return rc;
+      if (!self) {
+        rc = launch_slab_fwd<RA>(p, g, gs, Sg, b0 * C, nb * C, st);
+        if (rc) return rc;
+      }
+    }
+    {
+      Timer t(1, st, (self ? 1.0 : 2.0) * spec + (double)units * slots * K * 8.0, self ? "k_radial_power" : "k_radial_grad");
+      const tb::RadialArgs ra{p->dev, Sx, Sg, part, b0 * C, C, nb, self ? 1 : Cp, T, tpg, K, mode, inv_dr};
+      TB_HIP(launch_radial<RB>(ra, self, dim3(units, slots), lds, st));
+    }
+    {
+      Timer t(2, st, (double)units * slots * K * 8.0, "k_radial_sum");
+      const tb::RadialSumArgs sa{part, self ? out + (size_t)b0 * C * K : out, units, slots * K, scale,
+                                 (!self && b0 > 0) ? 1 : 0};
+      TB_HIP(tb::launch_radial_sum(sa, st));
+    }
+  }
+  return TB_OK;
+}
+
+static int radial_entry(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                        float* out, int Cp, int K, double dr, int mode, void* ws, size_t ws_bytes, int B, int C,
+                        void* stream) {
+  if (!ws || ws_bytes < tb_radial_workspace_bytes(p, B * C, K, g ? 1 : 0)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float inv_dr = (float)(1.0 / dr);
+#define TB_ARGS p, x, xs, g, gs, out, Cp, K, inv_dr, mode, ws, B, C, st
+  if (p->rset_wd == RS_SMALL)
+    return p->rset_h == RS_SMALL ? kspace_radial<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_radial<RS_SMALL, RS_ALL>(TB_ARGS);
+  return p->rset_h == RS_SMALL ? kspace_radial<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_radial<RS_ALL, RS_ALL>(TB_ARGS);
+#undef TB_ARGS
+}
+
+int tb_kspace_radial_power_f32(const tb_plan* p, const float* x, const int64_t* xs, float* P, int K, double dr,
+                               int mode, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+  if (!p || !x || !xs || !P || B < 1 || C < 1 || !radial_args_ok(K, dr, mode)) return TB_ERR_INVALID_ARG;
+  return radial_entry(p, x, xs, nullptr, nullptr, P, 1, K, dr, mode, ws, ws_bytes, B, C, stream);
+}
+
+int tb_kspace_radial_grad_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* g, const int64_t* gs,
+                              float* dp, int Cp, int K, double dr, int mode, void* ws, size_t ws_bytes, int B, int C,
+                              void* stream) {
+  if (!p || !x || !xs || !g || !gs || !dp || B < 1 || C < 1 || (Cp != 1 && Cp != C) || !radial_args_ok(K, dr, mode))
+    return TB_ERR_INVALID_ARG;
+  return radial_entry(p, x, xs, g, gs, dp, Cp, K, dr, mode, ws, ws_bytes, B, C, stream);
+}
+
+int tb_radial_mask_f32(const tb_plan* p, const float* prof, int Cp, int K, double dr, int mode, float* M, void* stream) {
+  if (!p || !prof || !M || Cp < 1 || !radial_args_ok(K, dr, mode)) return TB_ERR_INVALID_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const tb::RadialDenseArgs da{p->dev.H, p->dev.W, p->dev.D, Cp, K, mode, (float)(1.0 / dr), prof, M, nullptr, 0, 0};
+  TB_HIP(tb::launch_radial_expand(da, st));
+  return TB_OK;
+}
+
+int tb_radial_bin_f32(const tb_plan* p, const float* A, int Cm, int K, double dr, int mode, float* q, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (!p || !A || !q || Cm < 1 || !radial_args_ok(K, dr, mode)) return TB_ERR_INVALID_ARG;
+  const int64_t N = (int64_t)p->dev.H * p->dev.W * p->dev.D;
+  if (!ws || ws_bytes < (size_t)radial_bin_grid(N).units * Cm * K * sizeof(double)) return TB_ERR_WORKSPACE;
+  return radial_bin(p, A, Cm, K, (float)(1.0 / dr), mode, q, static_cast<double*>(ws),
+                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int tb_set_radial_fused(int enable) {
+  g_radial_fused = enable != 0;
+  return TB_OK;
+}
+
 // ------------------------------------------------------------ centred spectrum export / import (spectrum.h)
 // Tile of the export / import pass: pass B's width (one tile of LDS, whole 64-B segments per row, 16
 // columns = one 128-B line of 8-byte coefficients per row at H = 240), narrowed until the tile holds

@@ -9,6 +9,8 @@ Layering (DESIGN.md):
                      trainable module (LearnedKSpaceMask); their complex64 forms (ComplexKSpaceMask, ...)
   spectrum           the centred complex spectrum itself: shift_fourier / inv_shift_fourier on the
                      native passes, and the default-off drop-in switch of the Fourier helpers
+  radial             radial k-space profiles: the shell power spectrum (radial_power_spectrum), RadialFilter /
+                     RadialFilterd and the trainable LearnedRadialFilter
   pipeline           batched device-side augmentation stage (fused chain) for training
   unet / losses      MONAI-equivalent 3-D residual U-Net and DiceLoss (PyTorch-ROCm)
   train              train step, DDP over RCCL
@@ -27,8 +29,8 @@ for _d in ("FWD", "BWD", "WRW"):
 
 
 def __getattr__(name):
-    # texbias.spectrum without importing torch at package import
-    if name == "spectrum":
+    # texbias.spectrum / texbias.radial without importing torch at package import
+    if name in ("spectrum", "radial"):
         import importlib
-        return importlib.import_module(".spectrum", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -43,6 +43,12 @@ def _proto(L):
         "tb_mask_grad_workspace_bytes": (SZ, [P, I]),
         "tb_kspace_mask_grad_f32": (I, [P, P, P, P, P, P, I, P, SZ, I, I, P]),
         "tb_kspace_cmask_grad_f32": (I, [P, P, P, P, P, P, I, P, SZ, I, I, P]),
+        "tb_radial_workspace_bytes": (SZ, [P, I, I, I]),
+        "tb_kspace_radial_power_f32": (I, [P, P, P, P, I, C.c_double, I, P, SZ, I, I, P]),
+        "tb_kspace_radial_grad_f32": (I, [P, P, P, P, P, P, I, I, C.c_double, I, P, SZ, I, I, P]),
+        "tb_radial_mask_f32": (I, [P, P, I, I, C.c_double, I, P, P]),
+        "tb_radial_bin_f32": (I, [P, P, I, I, C.c_double, I, P, P, SZ, P]),
+        "tb_set_radial_fused": (I, [I]),
         "tb_spectrum_workspace_bytes": (SZ, [P, I]),
         "tb_kspace_export_f32": (I, [P, P, P, P, P, SZ, I, I, P]),
         "tb_kspace_import_f32": (I, [P, P, P, P, I, P, SZ, I, I, P]),

@@ -22,6 +22,12 @@ Reference interfaces each op replaces (file:line under the reference root):
   texbias::shift_fourier     Fourier.shift_fourier      filters_and_operators.py:594-612 (float32 -> complex64)
   texbias::inv_shift_fourier Fourier.inv_shift_fourier  filters_and_operators.py:614-632 (complex64 -> float32;
                              autograd: each is the other's adjoint up to N)
+  texbias::radial_power      the radially binned power spectrum the reference's notebooks look at by eye
+                             (show_slice_and_fourier); autograd w.r.t. the image
+  texbias::radial_filter     a mask that is a radial profile p(|f|) -- disk_mask (:136-197) is the 0/1 step --
+                             with autograd w.r.t. the image and the profile (the GD_work.ipynb variant of
+                             the Gibbs layer, trained by gradient instead of Gibbs_GD's finite differences)
+  texbias::radial_grad, radial_mask, radial_bin   the profile gradient, the expansion and its adjoint alone
   texbias::gibbs_layer       GibbsNoiseLayer.forward / _apply_mask  stylization_layers.py:79-116
                              (autograd: the filter is self-adjoint; d/d alpha = 0 as in the reference)
 """
@@ -336,6 +342,129 @@ def _inv_shift_fourier_backward(ctx, gy):
 
 shift_fourier.register_autograd(_shift_fourier_backward, setup_context=_shift_fourier_setup)
 inv_shift_fourier.register_autograd(_inv_shift_fourier_backward, setup_context=_inv_shift_fourier_setup)
+
+
+# ------------------------------------------------------------------ radial profiles (runtime.radial_*)
+@torch.library.custom_op("texbias::radial_mask", mutates_args=())
+def radial_mask(profile: torch.Tensor, spatial: Sequence[int], dr: float, mode: int) -> torch.Tensor:
+    """Expand a radial profile [K] or [C, K] to the centred mask of ``texbias::kspace_mask``: ``spatial`` or
+    ``(C,) + spatial``.  No autograd formula (``texbias::radial_filter`` has the gradient)."""
+    return rt.radial_mask(profile, spatial, dr, mode)
+
+
+@radial_mask.register_fake
+def _radial_mask_fake(profile, spatial, dr, mode):
+    sp = tuple(int(v) for v in spatial)
+    return profile.new_empty(sp if profile.dim() == 1 else (profile.shape[0],) + sp)
+
+
+@torch.library.custom_op("texbias::radial_bin", mutates_args=())
+def radial_bin(a: torch.Tensor, n_dims: int, bins: int, dr: float, mode: int) -> torch.Tensor:
+    """The adjoint of ``texbias::radial_mask``: a real centred array ``spatial`` or ``(C,) + spatial`` summed over
+    its radial bins, [bins] or [C, bins].  No autograd formula."""
+    return rt.radial_bin(a, n_dims, bins, dr, mode)
+
+
+@radial_bin.register_fake
+def _radial_bin_fake(a, n_dims, bins, dr, mode):
+    return a.new_empty((bins,) if a.dim() == n_dims else (a.shape[0], bins))
+
+
+@torch.library.custom_op("texbias::radial_grad", mutates_args=())
+def radial_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, channels: int, profile_channels: int, bins: int,
+                dr: float, mode: int) -> torch.Tensor:
+    """Gradient of ``radial_filter(x, p)`` with respect to the profile for the upstream gradient ``g``: [bins] for
+    ``profile_channels`` = 1 (summed over the channels), else [channels, bins]; summed over the samples.  No
+    autograd formula (double backward is not supported)."""
+    return rt.radial_grad(x, g, n_dims, profile_channels, bins, dr, mode, channels)
+
+
+@radial_grad.register_fake
+def _radial_grad_fake(x, g, n_dims, channels, profile_channels, bins, dr, mode):
+    return x.new_empty((bins,) if profile_channels == 1 else (profile_channels, bins))
+
+
+@torch.library.custom_op("texbias::radial_power", mutates_args=())
+def radial_power(x: torch.Tensor, n_dims: int, bins: int, dr: float, mode: int) -> torch.Tensor:
+    """Radially binned power spectrum of every volume of [*lead, *spatial]: [*lead, bins], with
+    P.sum(-1) = (x**2).sum(spatial).  Autograd with respect to ``x``, once differentiable."""
+    return rt.radial_power(x, n_dims, bins, dr, mode)
+
+
+@radial_power.register_fake
+def _radial_power_fake(x, n_dims, bins, dr, mode):
+    return x.new_empty(tuple(x.shape[: x.dim() - n_dims]) + (bins,))
+
+
+def _radial_power_setup(ctx, inputs, output):
+    x, n_dims, bins, dr, mode = inputs
+    ctx.save_for_backward(x)
+    ctx.n_dims, ctx.dr, ctx.mode = n_dims, dr, mode
+
+
+@torch.autograd.function.once_differentiable
+def _radial_power_backward(ctx, gp):
+    # P = x^T (F^H diag(w_k) F / N) x per volume, so gx = 2 Re(IFFT(M FFT x)) with M = expand(gP): one mask per
+    # volume, run as one sample of B C channels with a [B C][H][W][D] mask
+    (x,) = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    spatial = tuple(x.shape[x.dim() - ctx.n_dims:])
+    bc = int(np.prod(x.shape[: x.dim() - ctx.n_dims])) if x.dim() > ctx.n_dims else 1
+    prof = gp.reshape(bc, gp.shape[-1]).to(torch.float32).contiguous()
+    m = torch.ops.texbias.radial_mask(prof, list(spatial), ctx.dr, ctx.mode)
+    gx = torch.ops.texbias.kspace_mask(x.reshape((1, bc) + spatial), m, ctx.n_dims, bc, 0)
+    return gx.reshape(x.shape) * 2.0, None, None, None, None
+
+
+radial_power.register_autograd(_radial_power_backward, setup_context=_radial_power_setup)
+
+
+@torch.library.custom_op("texbias::radial_filter", mutates_args=())
+def radial_filter(x: torch.Tensor, profile: torch.Tensor, n_dims: int, channels: int, dr: float, mode: int,
+                  pad: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """y = kspace_mask(x, M) with M = radial_mask(profile): a k-space mask that is a function of radius, ``profile``
+    [K] (shared by every channel) or [channels, K].  The profile is expanded once per call (4 Cp N bytes,
+    independent of the batch size) and the image takes the existing TB_OP_MASK routes.  Returns (y, M); M is
+    a fresh tensor, kept for the backward.  Autograd with respect to ``x`` and ``profile``, each launched only
+    when asked for; once differentiable."""
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    m = rt.radial_mask(profile.detach(), spatial, dr, mode)
+    return rt.kspace_mask(x, m, n_dims, pad=pad, channels=channels), m
+
+
+@radial_filter.register_fake
+def _radial_filter_fake(x, profile, n_dims, channels, dr, mode, pad=0):
+    spatial = tuple(x.shape[x.dim() - n_dims:])
+    return (x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,)),
+            x.new_empty(spatial if profile.dim() == 1 else (profile.shape[0],) + spatial))
+
+
+def _radial_filter_setup(ctx, inputs, output):
+    x, profile, n_dims, channels, dr, mode, pad = inputs
+    ctx.save_for_backward(x, output[1])
+    ctx.mark_non_differentiable(output[1])
+    ctx.n_dims, ctx.channels, ctx.d, ctx.dr, ctx.mode = n_dims, channels, x.shape[-1], dr, mode
+    ctx.cp = 1 if profile.dim() == 1 else channels
+    ctx.bins, ctx.pshape = profile.shape[-1], tuple(profile.shape)
+
+
+@torch.autograd.function.once_differentiable
+def _radial_filter_backward(ctx, gy, gm):
+    # image: the real symmetric mask makes the filter self-adjoint; profile: the mask gradient summed over
+    # shells, without the dense dM; the zero pad columns take no gradient
+    x, m = ctx.saved_tensors
+    g = gy[..., : ctx.d]
+    gx = gp = None
+    if ctx.needs_input_grad[0]:
+        gx = torch.ops.texbias.kspace_mask(g, m, ctx.n_dims, ctx.channels, 0)
+    if ctx.needs_input_grad[1]:
+        gp = torch.ops.texbias.radial_grad(x, g, ctx.n_dims, ctx.channels, ctx.cp, ctx.bins, ctx.dr, ctx.mode)
+        gp = gp.reshape(ctx.pshape)   # [1, K] for one channel
+    return gx, gp, None, None, None, None, None
+
+
+radial_filter.register_autograd(_radial_filter_backward, setup_context=_radial_filter_setup)
 
 
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

@@ -32,7 +32,7 @@ def _kind(t) -> str:
 
 KSPACE = {"RandFourierDiskMaskd", "RandPlaneWaves_ellipsoid", "WrapArtifactd", "WrapArtifact", "GibbsNoise",
           "RandGibbsNoise", "RandGibbsNoised", "KSpaceSpikeNoise", "RandKSpaceSpikeNoise", "RandKSpaceSpikeNoised",
-          "KSpaceMask", "KSpaceMaskd", "ComplexKSpaceMask", "ComplexKSpaceMaskd"}
+          "KSpaceMask", "KSpaceMaskd", "ComplexKSpaceMask", "ComplexKSpaceMaskd", "RadialFilter", "RadialFilterd"}
 POINTWISE = {"SaltAndPepper"}
 CHANNEL = {"SelectChanneld", "MultimodalSlicesd"}
 
@@ -161,7 +161,8 @@ class FusedChain:
                         t.transforms[kk].set_random_state(t.common_seed)
                 if self.key in t.keys and t._do_transform:
                     prog += spike_program(t.transforms[self.key], c_cur, spatial)
-            elif k in ("KSpaceMask", "KSpaceMaskd", "ComplexKSpaceMask", "ComplexKSpaceMaskd"):
+            elif k in ("KSpaceMask", "KSpaceMaskd", "ComplexKSpaceMask", "ComplexKSpaceMaskd", "RadialFilter",
+                       "RadialFilterd"):   # texbias.radial: a profile, expanded to a mask the transform keeps
                 if not k.endswith("d") or self.key in t.keys:   # texbias.masks: the user's own mask, read on the device
                     prog += t.program(spatial, c_cur, self._dev)
             elif k == "SaltAndPepper":

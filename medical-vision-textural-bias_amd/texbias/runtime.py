@@ -359,7 +359,9 @@ def kspace_cmask_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, mask_channe
     return _mask_grad("kspace_cmask_grad", torch.complex64, x, g, n_dims, mask_channels, channels, out)
 
 
-def _mask_grad(what, dtype, x, g, n_dims, mask_channels, channels, out):
+def _grad_pair(what, x, g, n_dims, mask_channels, channels):
+    """Host-side check of an (image, upstream gradient) pair and their in-place addressing: (x, xs, g, gs,
+    spatial, channels, mask channels, volumes, geometry)."""
     if not isinstance(x, torch.Tensor) or not isinstance(g, torch.Tensor):
         raise ValueError(f"{what}: image and upstream gradient must be torch tensors")
     if n_dims < 1 or x.dim() < n_dims:
@@ -393,6 +395,12 @@ def _mask_grad(what, dtype, x, g, n_dims, mask_channels, channels, out):
 
     x, xs = strided(x)
     g, gs = strided(g)
+    return x, xs, g, gs, spatial, channels, cm, bc, geo
+
+
+def _mask_grad(what, dtype, x, g, n_dims, mask_channels, channels, out):
+    x, xs, g, gs, spatial, channels, cm, bc, geo = _grad_pair(what, x, g, n_dims, mask_channels, channels)
+    H, W, D = geo.hwd
     shape = spatial if cm == 1 else (cm,) + spatial
     if out is None:
         dm = torch.empty(shape, dtype=dtype, device=x.device)
@@ -497,6 +505,145 @@ def kspace_import(k: torch.Tensor, n_dims: int, pad: int = 0, out: Optional[torc
         check(lib().tb_kspace_import_f32(plan.handle, k.data_ptr(), y.data_ptr(), ys, pad, ws.data_ptr(), ws.numel(),
                                          bc, 1, _stream(k.device)), "tb_kspace_import_f32")
     return y
+
+
+# ------------------------------------------------------------------ radial profiles (tb_radial_*, csrc/radial.h)
+RADIAL_MODES = {"nearest": 0, "linear": 1}
+RADIAL_MAX_BINS = 2048
+
+
+def radial_params(what: str, bins, dr, mode) -> Tuple[int, float, int]:
+    """Host-side check of (bins, bin width, mode): ``mode`` is 0 / "nearest" or 1 / "linear"."""
+    if isinstance(mode, str):
+        if mode not in RADIAL_MODES:
+            raise ValueError(f"{what}: mode must be 'nearest' or 'linear', got {mode!r}")
+        mode = RADIAL_MODES[mode]
+    if isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError(f"{what}: mode must be 0 (nearest) or 1 (linear), got {mode!r}")
+    bins, dr = int(bins), float(dr)
+    if bins < 1 or bins > RADIAL_MAX_BINS:
+        raise ValueError(f"{what}: 1 <= bins <= {RADIAL_MAX_BINS} expected, got {bins}")
+    if not np.isfinite(dr) or dr <= 0.0:
+        raise ValueError(f"{what}: the bin width dr must be finite and > 0, got {dr}")
+    return bins, dr, int(mode)
+
+
+def _radial_out(what, out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+            or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"{what}: out must be a float32 contiguous {tuple(shape)} tensor on {device}")
+    return out
+
+
+def radial_power(x: torch.Tensor, n_dims: int, bins: int, dr: float = 1.0, mode=0,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Radially binned power spectrum of every volume of ``x`` [*lead, *spatial] (float32, any strides with a
+    contiguous last axis): P[..., k] = sum_f w_k(f) |FFT(x)(f)|^2 / N over ``bins`` shells of width ``dr`` of the
+    integer radius of the centred layout (``include/texbias.h``), so that P.sum(-1) = (x**2).sum(spatial).
+    One forward pass and one fused shell reduction in a fixed order (``tb_kspace_radial_power_f32``): no
+    spectrum is stored, repeated calls agree bit for bit.  Returns float32 [*lead, bins]."""
+    what = "radial_power"
+    K, dr, mode = radial_params(what, bins, dr, mode)
+    geo, bc = _spectrum_args(what, x, n_dims, torch.float32)
+    H, W, D = geo.hwd
+    xs = _image_strides(x, n_dims, geo)
+    if xs is None:
+        x = x.contiguous()
+        xs = _image_strides(x, n_dims, geo)
+    lead = tuple(x.shape[: x.dim() - n_dims])
+    ch = int(lead[-1]) if lead else 1   # launch groups of whole samples, as the other entry points
+    P = _radial_out(what, out, lead + (K,), x.device)
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_radial_workspace_bytes(plan.handle, bc, K, 0)))
+        check(lib().tb_kspace_radial_power_f32(plan.handle, x.data_ptr(), xs, P.data_ptr(), K, dr, mode, ws.data_ptr(),
+                                               ws.numel(), bc // ch, ch, _stream(x.device)),
+              "tb_kspace_radial_power_f32")
+    return P
+
+
+def radial_grad(x: torch.Tensor, g: torch.Tensor, n_dims: int, profile_channels: int, bins: int, dr: float = 1.0,
+                mode=1, channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``kspace_mask(x, radial_mask(p))`` with respect to the radial profile p for an upstream
+    gradient ``g``: dp[k] = sum_f w_k(f) Re(FFT(x)(f) conj(FFT(g)(f))) / N, summed over the samples and, with
+    ``profile_channels`` = 1, over the channels -- ``radial_bin(kspace_mask_grad(x, g))`` without the dense dM.
+    Arguments and strides as ``kspace_mask_grad``.  Returns float32 [bins] or [C, bins]
+    (``tb_kspace_radial_grad_f32``)."""
+    what = "radial_grad"
+    K, dr, mode = radial_params(what, bins, dr, mode)
+    x, xs, g, gs, spatial, channels, cp, bc, geo = _grad_pair(what, x, g, n_dims, profile_channels, channels)
+    H, W, D = geo.hwd
+    dp = _radial_out(what, out, (K,) if cp == 1 else (cp, K), x.device)
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_radial_workspace_bytes(plan.handle, bc, K, 1)))
+        check(lib().tb_kspace_radial_grad_f32(plan.handle, x.data_ptr(), xs, g.data_ptr(), gs, dp.data_ptr(), cp, K, dr,
+                                              mode, ws.data_ptr(), ws.numel(), bc // channels, channels,
+                                              _stream(x.device)), "tb_kspace_radial_grad_f32")
+    return dp
+
+
+def _radial_profile(what, p):
+    if not isinstance(p, torch.Tensor):
+        raise ValueError(f"{what}: a torch tensor is expected, got {type(p).__name__}")
+    if p.dim() not in (1, 2) or p.dtype != torch.float32:
+        raise ValueError(f"{what}: a float32 profile [K] or [C, K] is expected, got {p.dtype} {tuple(p.shape)}")
+    if p.device.type != "cuda":
+        raise TexbiasError(f"{what}: expected a HIP (cuda) tensor, got {p.device}")
+    return p.contiguous()
+
+
+def radial_mask(profile: torch.Tensor, spatial: Sequence[int], dr: float = 1.0, mode=1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Expand a radial profile [K] or [C, K] (float32, on the device) to the centred mask of ``kspace_mask``:
+    M[s] = sum_k w_k(s) p[k], shape ``spatial`` or ``(C,) + spatial`` (``tb_radial_mask_f32``)."""
+    what = "radial_mask"
+    p = _radial_profile(what, profile)
+    K, dr, mode = radial_params(what, p.shape[-1], dr, mode)
+    spatial = tuple(int(s) for s in spatial)
+    H, W, D = geometry(spatial).hwd
+    cp = 1 if p.dim() == 1 else int(p.shape[0])
+    M = _radial_out(what, out, spatial if p.dim() == 1 else (cp,) + spatial, p.device)
+    plan = plan_for(p.device, H, W, D)
+    with torch.cuda.device(p.device):
+        check(lib().tb_radial_mask_f32(plan.handle, p.data_ptr(), cp, K, dr, mode, M.data_ptr(), _stream(p.device)),
+              "tb_radial_mask_f32")
+    return M
+
+
+def radial_bin(a: torch.Tensor, n_dims: int, bins: int, dr: float = 1.0, mode=1,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of ``radial_mask``: q[k] = sum_s w_k(s) a[s] for a real array in the centred layout,
+    ``spatial`` (-> [bins]) or ``(C,) + spatial`` (-> [C, bins]), float32; float64 sums in a fixed order
+    (``tb_radial_bin_f32``).  ``radial_bin(ones)`` gives the shell counts."""
+    what = "radial_bin"
+    K, dr, mode = radial_params(what, bins, dr, mode)
+    if not isinstance(a, torch.Tensor):
+        raise ValueError(f"{what}: a torch tensor is expected, got {type(a).__name__}")
+    if a.dim() not in (n_dims, n_dims + 1) or a.dtype != torch.float32:
+        raise ValueError(f"{what}: a float32 array spatial or (C,) + spatial with {n_dims} spatial axes is expected, "
+                         f"got {a.dtype} {tuple(a.shape)}")
+    if a.device.type != "cuda":
+        raise TexbiasError(f"{what}: expected a HIP (cuda) tensor, got {a.device}")
+    a = a.contiguous()
+    H, W, D = geometry(tuple(a.shape[a.dim() - n_dims:])).hwd
+    cm = 1 if a.dim() == n_dims else int(a.shape[0])
+    q = _radial_out(what, out, (K,) if a.dim() == n_dims else (cm, K), a.device)
+    plan = plan_for(a.device, H, W, D)
+    with torch.cuda.device(a.device):
+        ws = workspace(a.device, int(lib().tb_radial_workspace_bytes(plan.handle, cm, K, 0)))
+        check(lib().tb_radial_bin_f32(plan.handle, a.data_ptr(), cm, K, dr, mode, q.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream(a.device)), "tb_radial_bin_f32")
+    return q
+
+
+def set_radial_fused(enable: bool) -> None:
+    """The fused shell reduction for ``radial_power`` / ``radial_grad`` when True (default), else the composed
+    route for every plan: ``kspace_mask_grad`` into the workspace, then the dense bin reduction
+    (tb_set_radial_fused; a test switch)."""
+    check(lib().tb_set_radial_fused(1 if enable else 0))
 
 
 def minmax_buffer(device: torch.device, B: int) -> torch.Tensor:

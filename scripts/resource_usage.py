@@ -19,7 +19,7 @@ rows = []
 for src in srcs:
     extra = ["-fno-slp-vectorize"] if src in NOSLP else []
     if src in ("kern_slab_fwd.hip", "kern_slab_inv.hip", "kern_kspace.hip", "kern_stats.hip",
-               "kern_maskgrad.hip", "kern_spectrum.hip"):
+               "kern_maskgrad.hip", "kern_spectrum.hip", "kern_radial.hip"):
         extra.append("-DTB_RS=1")
     with tempfile.TemporaryDirectory() as td:
         p = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-c", os.path.join(CSRC, src), "-o",
