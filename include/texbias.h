@@ -18,6 +18,9 @@
  *                          (one fused forward-FFT -> op program -> inverse-FFT round trip)
  *   tb_planes_closed_form_f32  RandPlaneWaves_ellipsoid.__call__ / KSpaceSpikeNoise._set_spike in
  *                          closed form (spike-only programs)                    :370-393, 966-983
+ *   tb_kspace_spikes_f32, tb_kspace_spikes_bwd_f32   spike_layer.forward       stylization_layers.py:143-151
+ *                          (KSpaceSpikeNoise._set_spike, filters_and_operators.py:906-983) with a device-resident
+ *                          log-intensity and its analytic gradients
  *   tb_salt_pepper_f32     SaltAndPepper.salt_and_pepper             filters_and_operators.py:465-482
  *   tb_minmax_f32          the x.max()/2, x.min()/2 of SaltAndPepper                   :476
  *   tb_disk_mask_f32       disk_mask.binary_mask_2d / binary_mask_3d                   :136-197
@@ -139,6 +142,45 @@ int tb_kspace_filter_f32(const tb_plan* plan, const float* x, const int64_t* xs,
 int tb_planes_closed_form_f32(const tb_plan* plan, const float* x, const int64_t* xs, float* y, const int64_t* ys,
                               int y_pad, void* ws, size_t ws_bytes, int B, int C, const tb_sample_ops* ops,
                               uint32_t* minmax, void* stream);
+
+/*
+ * The trainable spike layer: spike_layer.forward (stylization_layers.py:143-151), i.e. KSpaceSpikeNoise._set_spike
+ * (filters_and_operators.py:906-983) at S locations shared by every channel of every sample, on the closed-form
+ * route with the log-intensities read from DEVICE memory when the kernels run, and its analytic gradients (the
+ * reference updates the intensity by finite differences).  With f_j the unshifted frequency of spike j,
+ * theta_j(n) = 2 pi f_j . n / N, K_j = sum_n x[n] e^{-i theta_j(n)} per volume-channel, A_j = exp(I_j), m = |K_j|,
+ * u = K_j / m (u = 1 where m = 0):
+ *   forward   y  = x + Re( sum_j Delta_j e^{i theta_j} ) / N,   Delta_j = A_j u - K_j
+ *   backward  G_j = sum_n g[n] e^{-i theta_j(n)},  p + i q = conj(u) G_j   (g = dL/dy, real)
+ *             dI[j] = sum_{b,c} A_j p / N      (float64 sum in volume-channel order, stored as float32)
+ *             gx = g + Re( sum_j Gamma_j e^{i theta_j} ) / N,   Gamma_j = u (-p + i q (A_j / m - 1))
+ *             (Gamma_j = -G_j where m = 0: the phase is taken as constant there)
+ *   x, xs, y, ys, y_pad, minmax : as in tb_kspace_filter_f32;  g, gs / gx, gxs : the same indexing (a view of a
+ *             padded gradient without its pad columns is read in place)
+ *   loc   : HOST int32[S][3], the UNSHIFTED (kh, kw, kd) of each spike as in TB_OP_SPIKE; no two spikes at equal
+ *           or conjugate frequencies
+ *   logI  : DEVICE float[S]; values written to it in stream order before the launch, or between replays of a
+ *           captured graph, apply
+ *   coef  : DEVICE double[B*C][S][2], K_j of every volume-channel: written by the forward (or NULL: not kept),
+ *           read by the backward
+ *   gx    : DEVICE or NULL (no streaming pass is launched);  dI : DEVICE float[S] or NULL.  Both are overwritten
+ *           completely; no floating-point atomics, so repeated calls agree bit for bit
+ *   ws    : device workspace of >= tb_spikes_workspace_bytes(plan, B*C) bytes
+ * Forward: k_point_dft, k_spike_delta, k_point_apply.  Backward: k_point_dft on g, k_spike_gamma, k_spike_dI_sum
+ * when dI is given, k_point_apply on g when gx is given.  Batches above TB_MAX_BATCH are split by the library; no
+ * allocation, no host sync, launches on `stream` only (graph-capturable).  Before any launch: TB_ERR_INVALID_ARG
+ * for a null pointer, B < 1, C < 1, y_pad < 0, S outside 1..TB_MAX_OPS, a frequency out of range, two spikes at
+ * equal or conjugate frequencies, a null logI, or a null coef in the backward; TB_ERR_UNSUPPORTED_SIZE where the
+ * closed-form route's geometry or stride limits fail (D < 4, H > 2048, W > 1024, rows beyond 2^32 elements);
+ * TB_ERR_WORKSPACE for a missing or short workspace.
+ */
+size_t tb_spikes_workspace_bytes(const tb_plan* plan, int bc);
+int tb_kspace_spikes_f32(const tb_plan* plan, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
+                         void* ws, size_t ws_bytes, int B, int C, int S, const int32_t* loc, const float* logI,
+                         double* coef, uint32_t* minmax, void* stream);
+int tb_kspace_spikes_bwd_f32(const tb_plan* plan, const float* g, const int64_t* gs, int B, int C, int S,
+                             const int32_t* loc, const float* logI, const double* coef, float* gx, const int64_t* gxs,
+                             float* dI, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Salt and pepper over B samples of `rows` rows of `len` floats (row pitch `ld`, sample pitch `sb`):

@@ -12,6 +12,7 @@
 //                  min/max keys (the salt-and-pepper MIN/MAX of a chain that continues with S&P)
 // Algorithmic bytes: 4 B per voxel (dft) + 4 B in and 4 B (+ padding) out (apply).
 #include "point.h"
+#include "spike_grad.h"
 
 #include <map>
 #include <mutex>
@@ -340,6 +341,68 @@ __global__ __launch_bounds__(64) void k_point_delta(PointArgs) {
   }
 }
 
+// ---- the trainable spike layer (spike_grad.h): Delta and Gamma with the intensity read from device memory.
+// Both reduce the partials of k_point_dft in k_point_delta's order, one wave per volume-channel.
+__device__ __forceinline__ void spike_coef(const PointArgs& a, int bcl, int o, int lane, double& kr, double& ki) {
+  kr = 0.0, ki = 0.0;
+  for (int i = lane; i < a.parts; i += 64) {
+    const double* p = a.part + ((int64_t)(bcl * a.parts + i) * TB_MAX_OPS + o) * 2;
+    kr += p[0];
+    ki += p[1];
+  }
+  kr = wave_sum(kr);
+  ki = wave_sum(ki);
+}
+
+// Delta_j / N -> delta, K_j -> coef[bc][j] (kept for the backward)
+__global__ __launch_bounds__(64) void k_spike_delta(PointArgs) {
+  const PointArgs& a = kargs<PointArgs>();
+  const int bcl = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const double invN = 1.0 / ((double)a.H * (double)a.W * (double)a.D);
+  if (bcl == 0 && lane == 0) *a.cnt = 0u;  // k_point_apply's arrival counter
+  for (int o = 0; o < TB_MAX_OPS; ++o) {
+    float2 dl = make_float2(0.f, 0.f);
+    if (o < a.nspk) {
+      double kr, ki, dr, di;
+      spike_coef(a, bcl, o, lane, kr, ki);
+      spike_delta(kr, ki, exp((double)a.logI[o]), invN, dr, di);
+      dl = make_float2((float)dr, (float)di);
+      if (lane == 0 && a.coef) {
+        double* c = a.coef + ((int64_t)(a.bc0 + bcl) * a.nspk + o) * 2;
+        c[0] = kr;
+        c[1] = ki;
+      }
+    }
+    if (lane == 0) reinterpret_cast<float2*>(a.delta)[bcl * TB_MAX_OPS + o] = dl;
+  }
+}
+
+// the partials are those of the upstream gradient g: Gamma_j / N -> delta, A_j p / N -> share[bcl][j]
+__global__ __launch_bounds__(64) void k_spike_gamma(PointArgs) {
+  const PointArgs& a = kargs<PointArgs>();
+  const int bcl = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const double invN = 1.0 / ((double)a.H * (double)a.W * (double)a.D);
+  if (bcl == 0 && lane == 0) *a.cnt = 0u;
+  for (int o = 0; o < TB_MAX_OPS; ++o) {
+    float2 dl = make_float2(0.f, 0.f);
+    if (o < a.nspk) {
+      double gr, gi, cr, ci, sh;
+      spike_coef(a, bcl, o, lane, gr, gi);
+      const double* c = a.coef + ((int64_t)(a.bc0 + bcl) * a.nspk + o) * 2;
+      spike_gamma(c[0], c[1], gr, gi, exp((double)a.logI[o]), invN, cr, ci, sh);
+      dl = make_float2((float)cr, (float)ci);
+      if (lane == 0) a.share[bcl * a.nspk + o] = sh;
+    }
+    if (lane == 0) reinterpret_cast<float2*>(a.delta)[bcl * TB_MAX_OPS + o] = dl;
+  }
+}
+
+// dI[j]: the shares of the launch group's volume-channels added in index order (float64), one thread a spike
+__global__ __launch_bounds__(64) void k_spike_dI_sum(SpikeSumArgs a) {
+  const int j = (int)threadIdx.x;
+  if (j < a.S) spike_dI_store(a, j, spike_dI_sum(a, j));
+}
+
 template <int NA>
 __global__ __launch_bounds__(POINT_NT) void k_point_apply(PointArgs) {
   const PointArgs& a = kargs<PointArgs>();
@@ -537,12 +600,21 @@ hipError_t launch_point(const PointArgs& a, hipStream_t st, int stage) {
     hipLaunchKernelGGL(kd, dim3(a.parts, a.nbc), dim3(POINT_NT), point_lds(a, 0), st, a);
   } else if (stage == 1) {
     hipLaunchKernelGGL(k_point_delta, dim3(a.nbc), dim3(64), 0, st, a);
+  } else if (stage == 3) {
+    hipLaunchKernelGGL(k_spike_delta, dim3(a.nbc), dim3(64), 0, st, a);
+  } else if (stage == 4) {
+    hipLaunchKernelGGL(k_spike_gamma, dim3(a.nbc), dim3(64), 0, st, a);
   } else {
     const auto ka = a.namax == 1 ? k_point_apply<1> : k_point_apply<TB_MAX_OPS>;
     const hipError_t e = allow_lds(ka, point_lds(a, 2));
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ka, dim3(a.parts_apply, a.nbc), dim3(POINT_NT), point_lds(a, 2), st, a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_spike_dI_sum(const SpikeSumArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(k_spike_dI_sum, dim3(1), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

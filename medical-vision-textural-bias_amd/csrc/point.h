@@ -34,6 +34,11 @@ struct PointArgs {
   float2* mmp;            // [nbc][parts] per-workgroup (min, max) of the output
   uint32_t* cnt;          // arrival counter of the apply workgroups (zeroed by k_point_delta)
   BatchOps ops;
+  // the trainable spike layer (spike_grad.h): k_spike_delta / k_spike_gamma only
+  const float* logI = nullptr;  // DEVICE [nspk] log-intensities I_j (read when the kernel runs)
+  double* coef = nullptr;       // [all bc][nspk][2] K_j of the forward (absolute bc), or null
+  double* share = nullptr;      // [nbc][nspk] A_j p / N of this launch group
+  int nspk = 0;                 // spikes of the layer: every sample's program is these, chan = -1
 };
 
 // workspace carve for nbc volume-channels
@@ -64,6 +69,9 @@ inline bool point_strides_ok(int H, int W, int D, int ypad, const int64_t* xs, c
 // Sets a.parts / a.parts_apply: one round of resident workgroups per launch (ncu x occupancy, at most
 // POINT_WG), split evenly over the launch's volume-channels.
 void point_grid(PointArgs& a, int ncu);
-hipError_t launch_point(const PointArgs& a, hipStream_t st, int stage);  // stage 0: K, 1: Delta, 2: apply
+// stage 0: K, 1: Delta, 2: apply; 3: k_spike_delta, 4: k_spike_gamma (in place of 1)
+hipError_t launch_point(const PointArgs& a, hipStream_t st, int stage);
+struct SpikeSumArgs;
+hipError_t launch_spike_dI_sum(const SpikeSumArgs& a, hipStream_t st);
 
 }  // namespace tb

@@ -25,6 +25,7 @@
 #include "point.h"
 #include "plan_host.h"
 #include "sap_core.h"
+#include "spike_grad.h"
 #include "wrap.h"
 
 using namespace tb;
@@ -1485,6 +1486,138 @@ int tb_planes_closed_form_f32(const tb_plan* p, const float* x, const int64_t* x
     const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
     const int rc = run_point(p, x, xs, y, ys, y_pad, static_cast<char*>(ws), b0, nb, C, ops, minmax, st);
     if (rc) return rc;
+  }
+  return TB_OK;
+}
+
+// ------------------------------------------------------------ trainable spike layer (spike_grad.h)
+// spike_layer.forward (stylization_layers.py:143-151) = KSpaceSpikeNoise._set_spike
+// (filters_and_operators.py:906-983) at one location for every channel, with the log-intensity read from
+// device memory and the analytic gradients in place of the reference's finite differences.
+// Workspace: the closed-form route's carve for the launch group, then its float64 dI shares.
+static size_t spikes_share_bytes(int nbc) { return ((size_t)nbc * TB_MAX_OPS * sizeof(double) + 255) & ~(size_t)255; }
+
+size_t tb_spikes_workspace_bytes(const tb_plan* plan, int bc) {
+  if (!plan || bc < 1) return 0;
+  return tb::point_ws(bc).total + spikes_share_bytes(bc);
+}
+
+// the layer's host program (S spikes on every channel); argument errors before geometry limits
+static int spikes_program(const tb_plan* p, int S, const int32_t* loc, tb_sample_ops& so) {
+  if (S < 1 || S > TB_MAX_OPS || !loc) return TB_ERR_INVALID_ARG;
+  const int n[3] = {p->dev.H, p->dev.W, p->dev.D};
+  std::memset(&so, 0, sizeof(so));
+  so.n = S;
+  for (int j = 0; j < S; ++j) {
+    tb_op& op = so.op[j];
+    op.kind = TB_OP_SPIKE;
+    op.chan = -1;
+    op.f[1] = NAN;  // own phase
+    for (int ax = 0; ax < 3; ++ax) {
+      if (loc[3 * j + ax] < 0 || loc[3 * j + ax] >= n[ax]) return TB_ERR_INVALID_ARG;
+      op.i[ax] = loc[3 * j + ax];
+    }
+    for (int q = 0; q < j; ++q) {
+      bool same = true, conj = true;
+      for (int ax = 0; ax < 3; ++ax) {
+        same &= op.i[ax] == so.op[q].i[ax];
+        conj &= op.i[ax] == (n[ax] - so.op[q].i[ax]) % n[ax];
+      }
+      if (same || conj) return TB_ERR_INVALID_ARG;
+    }
+  }
+  return tb::point_program(so, n[0], n[1], n[2]) ? TB_OK : TB_ERR_UNSUPPORTED_SIZE;
+}
+
+// launch arguments of one launch group: x -> y through the spikes `so` (y null: no apply is launched)
+static tb::PointArgs spikes_group(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys,
+                                  int y_pad, char* ws, int b0, int nb, int C, const tb_sample_ops& so,
+                                  const float* logI, double* coef, uint32_t* minmax) {
+  tb::PointArgs a;
+  std::memset(&a, 0, sizeof(a));
+  const int nbc = nb * C;
+  a.H = p->dev.H, a.W = p->dev.W, a.D = p->dev.D;
+  a.x = x, a.xsbc = xs[0], a.xsh = xs[1], a.xsw = xs[2];
+  a.y = y, a.ysbc = ys[0], a.ysh = ys[1], a.ysw = ys[2];
+  a.ypad = y_pad, a.bc0 = b0 * C, a.C = C, a.nbc = nbc, a.mm = minmax;
+  const tb::PointWs wl = tb::point_ws(nbc);
+  a.part = reinterpret_cast<double*>(ws + wl.part);
+  a.delta = reinterpret_cast<float*>(ws + wl.delta);
+  a.mmp = reinterpret_cast<float2*>(ws + wl.mmp);
+  a.cnt = reinterpret_cast<uint32_t*>(ws + wl.cnt);
+  a.share = reinterpret_cast<double*>(ws + wl.total);
+  a.namax = so.n;
+  for (int i = 0; i < nb; ++i) a.ops.s[i] = so;
+  a.logI = logI, a.coef = coef, a.nspk = so.n;
+  tb::point_grid(a, p->ncu);
+  return a;
+}
+
+int tb_kspace_spikes_f32(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
+                         void* ws, size_t ws_bytes, int B, int C, int S, const int32_t* loc, const float* logI,
+                         double* coef, uint32_t* minmax, void* stream) {
+  if (!p || !x || !xs || !y || !ys || B < 1 || C < 1 || y_pad < 0 || !logI) return TB_ERR_INVALID_ARG;
+  tb_sample_ops so;
+  const int rc = spikes_program(p, S, loc, so);
+  if (rc) return rc;
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D;
+  if (!tb::point_strides_ok(H, W, D, y_pad, xs, ys)) return TB_ERR_UNSUPPORTED_SIZE;
+  if (!ws || ws_bytes < tb_spikes_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const tb::PointArgs a = spikes_group(p, x, xs, y, ys, y_pad, static_cast<char*>(ws), b0, nb, C, so, logI, coef, minmax);
+    const double vox = (double)a.nbc * H * W * D;
+    {
+      Timer t(0, st, vox * 4.0, "k_point_dft");
+      TB_HIP(tb::launch_point(a, st, 0));
+    }
+    {
+      Timer t(1, st, (double)a.nbc * a.parts * TB_MAX_OPS * 16.0, "k_spike_delta");
+      TB_HIP(tb::launch_point(a, st, 3));
+    }
+    {
+      Timer t(2, st, vox * 4.0 + (double)a.nbc * H * W * (D + y_pad) * 4.0, "k_point_apply");
+      TB_HIP(tb::launch_point(a, st, 2));
+    }
+  }
+  return TB_OK;
+}
+
+int tb_kspace_spikes_bwd_f32(const tb_plan* p, const float* g, const int64_t* gs, int B, int C, int S,
+                             const int32_t* loc, const float* logI, const double* coef, float* gx, const int64_t* gxs,
+                             float* dI, void* ws, size_t ws_bytes, void* stream) {
+  if (!p || !g || !gs || B < 1 || C < 1 || !logI || !coef || (gx && !gxs)) return TB_ERR_INVALID_ARG;
+  tb_sample_ops so;
+  const int rc = spikes_program(p, S, loc, so);
+  if (rc) return rc;
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D;
+  const int64_t* os = gx ? gxs : gs;
+  if (!tb::point_strides_ok(H, W, D, 0, gs, os)) return TB_ERR_UNSUPPORTED_SIZE;
+  if (!ws || ws_bytes < tb_spikes_workspace_bytes(p, B * C)) return TB_ERR_WORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const tb::PointArgs a = spikes_group(p, g, gs, gx, os, 0, static_cast<char*>(ws), b0, nb, C, so, logI,
+                                         const_cast<double*>(coef), nullptr);
+    const double vox = (double)a.nbc * H * W * D;
+    {
+      Timer t(0, st, vox * 4.0, "k_point_dft");
+      TB_HIP(tb::launch_point(a, st, 0));
+    }
+    {
+      Timer t(1, st, (double)a.nbc * a.parts * TB_MAX_OPS * 16.0, "k_spike_gamma");
+      TB_HIP(tb::launch_point(a, st, 4));
+    }
+    if (dI) {
+      Timer t(3, st, (double)a.nbc * S * 8.0, "k_spike_dI_sum");  // its own slot: slot 2 is the apply's
+      const tb::SpikeSumArgs sa{a.share, dI, a.nbc, S, b0 > 0 ? 1 : 0};
+      TB_HIP(tb::launch_spike_dI_sum(sa, st));
+    }
+    if (gx) {
+      Timer t(2, st, vox * 8.0, "k_point_apply");
+      TB_HIP(tb::launch_point(a, st, 2));
+    }
   }
   return TB_OK;
 }

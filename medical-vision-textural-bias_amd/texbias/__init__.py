@@ -11,6 +11,8 @@ Layering (DESIGN.md):
                      native passes, and the default-off drop-in switch of the Fourier helpers
   radial             radial k-space profiles: the shell power spectrum (radial_power_spectrum), RadialFilter /
                      RadialFilterd and the trainable LearnedRadialFilter
+  spikes             the trainable spike layer (LearnedSpikeLayer): device-resident log-intensities with
+                     closed-form gradients with respect to them and to the image
   pipeline           batched device-side augmentation stage (fused chain) for training
   unet / losses      MONAI-equivalent 3-D residual U-Net and DiceLoss (PyTorch-ROCm)
   train              train step, DDP over RCCL
@@ -29,8 +31,8 @@ for _d in ("FWD", "BWD", "WRW"):
 
 
 def __getattr__(name):
-    # texbias.spectrum / texbias.radial without importing torch at package import
-    if name in ("spectrum", "radial"):
+    # texbias.spectrum / texbias.radial / texbias.spikes without importing torch at package import
+    if name in ("spectrum", "radial", "spikes"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -30,6 +30,11 @@ Reference interfaces each op replaces (file:line under the reference root):
   texbias::radial_grad, radial_mask, radial_bin   the profile gradient, the expansion and its adjoint alone
   texbias::gibbs_layer       GibbsNoiseLayer.forward / _apply_mask  stylization_layers.py:79-116
                              (autograd: the filter is self-adjoint; d/d alpha = 0 as in the reference)
+  texbias::kspace_spikes     spike_layer.forward  stylization_layers.py:143-151 (KSpaceSpikeNoise._set_spike,
+                             filters_and_operators.py:906-983) with the log-intensity read on the device; autograd
+                             w.r.t. the image and the log-intensity in closed form (the reference's drivers update
+                             it by finite differences, spikes11_layer_domain_GD.py:260-275)
+  texbias::kspace_spikes_grad   the two gradients on their own
 """
 from __future__ import annotations
 
@@ -465,6 +470,78 @@ def _radial_filter_backward(ctx, gy, gm):
 
 
 radial_filter.register_autograd(_radial_filter_backward, setup_context=_radial_filter_setup)
+
+
+# ------------------------------------------------------------------ trainable spikes (runtime.kspace_spikes*)
+@torch.library.custom_op("texbias::kspace_spikes", mutates_args=())
+def kspace_spikes(x: torch.Tensor, log_intensity: torch.Tensor, loc: Sequence[int], n_dims: int, channels: int,
+                  pad: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The spike layer: |K(f_j)| := exp(log_intensity[j]) at S centred locations on every channel of
+    [B*channels..., *spatial], phase kept (last axis padded by ``pad`` zero columns).  ``loc``: flat list of
+    S * n_dims indices into the layout of ``Fourier.shift_fourier`` (the reference's ``loc``), no two at equal or
+    conjugate frequencies; ``log_intensity``: float32 [S] on x's device, read by the kernels on the current stream
+    (no host sync).  Returns (y, coef), coef float64 [*lead, S, 2] = K(f_j) of x, kept for the backward.  Autograd
+    with respect to ``x`` and ``log_intensity``, each launched only when asked for; once differentiable."""
+    return rt.kspace_spikes(x, log_intensity, loc, n_dims, channels, pad)
+
+
+def _spikes_count(loc, n_dims: int) -> int:
+    if n_dims < 1 or len(loc) % n_dims or not len(loc):
+        raise ValueError(f"texbias::kspace_spikes: {len(loc)} location indices for {n_dims} transformed axes")
+    return len(loc) // n_dims
+
+
+@kspace_spikes.register_fake
+def _kspace_spikes_fake(x, log_intensity, loc, n_dims, channels, pad=0):
+    S = _spikes_count(loc, n_dims)
+    lead = tuple(x.shape[: x.dim() - n_dims])
+    return (x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,)),
+            x.new_empty(lead + (S, 2), dtype=torch.float64))
+
+
+@torch.library.custom_op("texbias::kspace_spikes_grad", mutates_args=())
+def kspace_spikes_grad(g: torch.Tensor, coef: torch.Tensor, log_intensity: torch.Tensor, loc: Sequence[int],
+                       n_dims: int, channels: int, image_grad: bool,
+                       intensity_grad: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gradients of ``kspace_spikes`` for the upstream gradient ``g`` (the image's shape, any strides with a
+    contiguous last axis) and the ``coef`` of its forward: (gx, dI), dI float32 [S] summed over every
+    volume-channel.  ``image_grad`` False: no streaming pass is launched and gx is an empty tensor;
+    ``intensity_grad`` False: the ordered sum is not launched and dI is an empty tensor.  No autograd formula
+    (double backward is not supported)."""
+    gx, dI = rt.kspace_spikes_grad(g, coef, log_intensity, loc, n_dims, channels, image_grad, intensity_grad)
+    return (gx if image_grad else g.new_empty((0,))), (dI if intensity_grad else g.new_empty((0,)))
+
+
+@kspace_spikes_grad.register_fake
+def _kspace_spikes_grad_fake(g, coef, log_intensity, loc, n_dims, channels, image_grad, intensity_grad=True):
+    S = _spikes_count(loc, n_dims)
+    return g.new_empty(g.shape if image_grad else (0,)), g.new_empty((S,) if intensity_grad else (0,))
+
+
+def _kspace_spikes_setup(ctx, inputs, output):
+    x, log_intensity, loc, n_dims, channels, pad = inputs
+    ctx.save_for_backward(output[1], log_intensity)
+    ctx.mark_non_differentiable(output[1])
+    ctx.loc, ctx.n_dims, ctx.channels, ctx.d = [int(v) for v in loc], n_dims, channels, x.shape[-1]
+
+
+@torch.autograd.function.once_differentiable
+def _kspace_spikes_backward(ctx, gy, gcoef):
+    # one coefficient per spike of the upstream gradient, then Gamma_j and the dI shares (csrc/spike_grad.h); the
+    # image gradient is one more plane-wave add and the intensity gradient one ordered sum, each launched only
+    # when asked for; the zero pad columns take no gradient, and the view without them is read in place
+    coef, log_intensity = ctx.saved_tensors
+    gx = dI = None
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        rx, rI = torch.ops.texbias.kspace_spikes_grad(gy[..., : ctx.d], coef, log_intensity.detach(), ctx.loc, ctx.n_dims,
+                                                      ctx.channels, bool(ctx.needs_input_grad[0]),
+                                                      bool(ctx.needs_input_grad[1]))
+        gx = rx if ctx.needs_input_grad[0] else None
+        dI = rI if ctx.needs_input_grad[1] else None
+    return gx, dI, None, None, None, None
+
+
+kspace_spikes.register_autograd(_kspace_spikes_backward, setup_context=_kspace_spikes_setup)
 
 
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

@@ -17,7 +17,7 @@ import torch
 
 from ._abi import TB_MAX_BATCH, TB_MAX_OPS, programs_array
 from ._lib import TexbiasError, check, lib
-from .kprog import Geometry, cmask_op, geometry, mask_op, split_program
+from .kprog import Geometry, cmask_op, geometry, mask_op, split_program, unshift
 
 _plans: Dict[Tuple[int, int, int, int], "Plan"] = {}
 _ws: "OrderedDict[Tuple[int, int], torch.Tensor]" = OrderedDict()
@@ -644,6 +644,162 @@ def set_radial_fused(enable: bool) -> None:
     route for every plan: ``kspace_mask_grad`` into the workspace, then the dense bin reduction
     (tb_set_radial_fused; a test switch)."""
     check(lib().tb_set_radial_fused(1 if enable else 0))
+
+
+# ------------------------------------------------------------------ trainable spikes (tb_kspace_spikes_*, csrc/spike_grad.h)
+def spikes_touch(a: Sequence[int], b: Sequence[int], n: Sequence[int]) -> bool:
+    """Two unshifted frequencies reach the same stored coefficient: equal, or conjugate (a = -b mod n)."""
+    a, b = tuple(int(v) for v in a), tuple(int(v) for v in b)
+    return a == b or a == tuple((m - v) % m for v, m in zip(b, n))
+
+
+def spike_locations(what: str, loc: Sequence[int], spatial: Sequence[int]) -> List[Tuple[int, int, int]]:
+    """Host-side check of the spikes of one call: ``loc`` is a flat list of S * n_dims indices into the CENTRED
+    layout of ``Fourier.shift_fourier`` (the reference's ``loc``).  Returns the S unshifted (kh, kw, kd) of
+    ``TB_OP_SPIKE``.  IndexError for an index out of bounds; ValueError for a count outside 1..TB_MAX_OPS or
+    two spikes at equal or conjugate frequencies.  Touches no device."""
+    spatial = tuple(int(s) for s in spatial)
+    geo = geometry(spatial)
+    loc = [int(v) for v in loc]
+    nd = len(spatial)
+    if nd < 1 or not loc or len(loc) % nd:
+        raise ValueError(f"{what}: {len(loc)} location indices for {nd} transformed axes")
+    S = len(loc) // nd
+    if not 1 <= S <= TB_MAX_OPS:
+        raise ValueError(f"{what}: {S} spikes (1 to {TB_MAX_OPS} are supported)")
+    out: List[Tuple[int, int, int]] = []
+    for j in range(S):
+        idx = loc[j * nd:(j + 1) * nd]
+        for s, n in zip(idx, spatial):
+            if not 0 <= s < n:
+                raise IndexError(f"{what}: spike index {tuple(idx)} out of bounds for {spatial}")
+        f = geo.to_hwd(unshift(idx, spatial))
+        for q, e in enumerate(out):
+            if spikes_touch(f, e, geo.hwd):
+                raise ValueError(f"{what}: spikes {q} and {j} are at equal or conjugate frequencies")
+        out.append(f)
+    return out
+
+
+def spike_intensity(what: str, log_intensity, S: int, device=None) -> None:
+    """Host-side check of the layer's log-intensities: a float32 tensor [S] (on ``device`` when given)."""
+    if not isinstance(log_intensity, torch.Tensor):
+        raise ValueError(f"{what}: log_intensity must be a torch tensor, got {type(log_intensity).__name__}")
+    if tuple(log_intensity.shape) != (S,):
+        raise ValueError(f"{what}: log_intensity {tuple(log_intensity.shape)} for {S} spikes (expected ({S},))")
+    if log_intensity.dtype != torch.float32:
+        raise ValueError(f"{what}: log_intensity must be float32, got {log_intensity.dtype}")
+    if device is not None and log_intensity.device != device:
+        raise ValueError(f"{what}: log_intensity on {log_intensity.device}, image on {device}")
+
+
+def _spikes_args(what, t, log_intensity, loc, n_dims, channels):
+    """Common host-side checks of the two spike launchers: (unshifted locations as int32[S][3], S, geometry,
+    volumes, channels)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a torch tensor is expected, got {type(t).__name__}")
+    n_dims, channels = int(n_dims), int(channels)
+    if n_dims < 1 or t.dim() < n_dims:
+        raise ValueError(f"{what}: {n_dims} transformed axes on a {t.dim()}-d tensor")
+    spatial = tuple(t.shape[t.dim() - n_dims:])
+    lead = t.shape[: t.dim() - n_dims]
+    bc = int(np.prod(lead)) if len(lead) else 1
+    if channels < 1 or bc % channels:
+        raise ValueError(f"{what}: {channels} channels do not divide the leading axes {tuple(lead)}")
+    f = spike_locations(what, loc, spatial)
+    spike_intensity(what, log_intensity, len(f), t.device)
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: float32 expected, got {t.dtype}")
+    return f, len(f), geometry(spatial), bc, channels
+
+
+def _spikes_loc_array(f):
+    return (C.c_int32 * (3 * len(f)))(*[v for k in f for v in k])
+
+
+def kspace_spikes(x: torch.Tensor, log_intensity: torch.Tensor, loc: Sequence[int], n_dims: int, channels: int,
+                  pad: int = 0, minmax: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The spike layer on the closed-form route with a device-resident log-intensity: |K(f_j)| := exp(I_j) at the S
+    centred locations ``loc`` (flat, S * n_dims indices) on every channel of ``x`` [*lead, *spatial], phase kept.
+    ``log_intensity``: float32 [S] on x's device, read when the kernels run (no host sync: a captured graph
+    replays with the values then in the tensor).  Returns (y, coef): y as ``kspace_filter`` (``pad`` zero
+    columns), coef float64 [*lead, S, 2] = the coefficients K(f_j) of x, which ``kspace_spikes_grad`` needs
+    (``tb_kspace_spikes_f32``)."""
+    what = "kspace_spikes"
+    f, S, geo, bc, channels = _spikes_args(what, x, log_intensity, loc, n_dims, channels)
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError(f"{what}: pad must be >= 0, got {pad}")
+    require_hip(x, what)
+    H, W, D = geo.hwd
+    if pad and len(geo.kept) and geo.kept[-1] != n_dims - 1:
+        raise TexbiasError("padding requires a non-singleton last axis")
+    xs = _image_strides(x, n_dims, geo)
+    if xs is None:
+        x = x.contiguous()
+        xs = _image_strides(x, n_dims, geo)
+    y = torch.empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,), dtype=torch.float32, device=x.device)
+    ys = _image_strides(y, n_dims, geo)
+    coef = torch.empty(tuple(x.shape[: x.dim() - n_dims]) + (S, 2), dtype=torch.float64, device=x.device)
+    logi = log_intensity.detach().contiguous()
+    mm_ptr = None
+    if minmax is not None:
+        if minmax.dtype != torch.int32 or minmax.numel() < 2 * (bc // channels) or minmax.device != x.device:
+            raise TexbiasError("minmax must be an int32 [B,2] tensor on the input's device")
+        mm_ptr = minmax.data_ptr()
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_spikes_workspace_bytes(plan.handle, bc)))
+        check(lib().tb_kspace_spikes_f32(plan.handle, x.data_ptr(), xs, y.data_ptr(), ys, pad, ws.data_ptr(), ws.numel(),
+                                         bc // channels, channels, S, _spikes_loc_array(f), logi.data_ptr(),
+                                         coef.data_ptr(), mm_ptr, _stream(x.device)), "tb_kspace_spikes_f32")
+    return y, coef
+
+
+def kspace_spikes_grad(g: torch.Tensor, coef: torch.Tensor, log_intensity: torch.Tensor, loc: Sequence[int],
+                       n_dims: int, channels: int, image_grad: bool = True, intensity_grad: bool = True,
+                       gx_out: Optional[torch.Tensor] = None,
+                       dI_out: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The gradients of ``kspace_spikes`` for an upstream gradient ``g`` (the image's shape, any strides with a
+    contiguous last axis: ``gy[..., :D]`` of a padded output is read in place) and the ``coef`` of its forward:
+    (gx, dI) with gx = g + Re(sum_j Gamma_j e^{i theta_j}) / N (``image_grad``, one more read and write of the
+    volume; None otherwise and no streaming pass is launched) and dI float32 [S], summed over every
+    volume-channel in index order in float64 (``intensity_grad``).  No floating-point atomics: repeated calls
+    agree bit for bit (``tb_kspace_spikes_bwd_f32``).  ``gx_out`` / ``dI_out``: float32 contiguous tensors of the
+    results' shapes on g's device to overwrite (they need not be zeroed)."""
+    what = "kspace_spikes_grad"
+    f, S, geo, bc, channels = _spikes_args(what, g, log_intensity, loc, n_dims, channels)
+    lead = tuple(g.shape[: g.dim() - n_dims])
+    if (not isinstance(coef, torch.Tensor) or tuple(coef.shape) != lead + (S, 2) or coef.dtype != torch.float64
+            or coef.device != g.device):
+        raise ValueError(f"{what}: coef must be a float64 {lead + (S, 2)} tensor on {g.device}")
+    require_hip(g, what)
+    H, W, D = geo.hwd
+    gs = _image_strides(g, n_dims, geo)
+    if gs is None:
+        g = g.contiguous()
+        gs = _image_strides(g, n_dims, geo)
+    coef = coef.contiguous()
+    logi = log_intensity.detach().contiguous()
+    def result(out, shape, name):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=g.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+                or not out.is_contiguous() or out.device != g.device):
+            raise ValueError(f"{what}: {name} must be a float32 contiguous {tuple(shape)} tensor on {g.device}")
+        return out
+
+    gx = result(gx_out, g.shape, "gx_out") if image_grad else None
+    dI = result(dI_out, (S,), "dI_out") if intensity_grad else None
+    plan = plan_for(g.device, H, W, D)
+    with torch.cuda.device(g.device):
+        ws = workspace(g.device, int(lib().tb_spikes_workspace_bytes(plan.handle, bc)))
+        check(lib().tb_kspace_spikes_bwd_f32(
+            plan.handle, g.data_ptr(), gs, bc // channels, channels, S, _spikes_loc_array(f), logi.data_ptr(),
+            coef.data_ptr(), gx.data_ptr() if image_grad else None,
+            _image_strides(gx, n_dims, geo) if image_grad else None, dI.data_ptr() if intensity_grad else None,
+            ws.data_ptr(), ws.numel(), _stream(g.device)), "tb_kspace_spikes_bwd_f32")
+    return gx, dI
 
 
 def minmax_buffer(device: torch.device, B: int) -> torch.Tensor:
