@@ -324,6 +324,50 @@ int tb_kspace_import_f32(const tb_plan* plan, const void* K, float* y, const int
                          size_t ws_bytes, int B, int C, void* stream);
 
 /*
+ * Amplitude mixing in k-space (Fourier domain adaptation, amplitude mix / swap): sample b keeps the phase of
+ * its spectrum and moves its amplitude towards that of a partner image, weighted by a real mask,
+ *   X = fftshift(fftn(x[b])),  Y = fftshift(fftn(y[perm[b]])),  m = lam[b] M
+ *   out[b] = Re(ifftn(ifftshift( polar((1 - m) |X| + m |Y|, angle(X)) )))
+ * evaluated on the stored half spectrum as X' = (1 - m_s) X + m_s |Y| X / |X| with the symmetrised
+ * m_s(f) = lam[b] (M[s(f)] + M[s(-f)]) / 2 (exact: K is affine in M) and X / |X| = 1 where X = 0.  No
+ * spectrum leaves the workspace.
+ *   x, xs     : the image, indexed as in tb_kspace_filter_f32
+ *   y, ys_in  : the partner images, same shape with their own strides; y = NULL takes the partners from x
+ *               (batch-internal mixing: one set of forward passes)
+ *   perm      : device int32 [B], the partner sample of each sample, or NULL for the identity.  Read on the
+ *               device and clamped to [0, B): a value outside is never dereferenced, but the caller owes a
+ *               valid index.  It need not be a permutation
+ *   M, Cm     : device, contiguous float32 [Cm][H][W][D] in the centred layout of TB_OP_MASK, Cm = 1 or C
+ *   lam       : device float32 [B], read by the kernel (no host read)
+ *   out, outs : the output image, indexed like x; out_pad zero columns are written after D
+ *   ws        : device workspace of >= tb_ampmix_workspace_bytes(plan, B*C, 0, 0) bytes
+ * Backward, for an upstream gradient g (image shape, strides gs), with G = FFT(g), u = X / |X|, v = Y / |Y|
+ * and c = Re(conj(u) G):
+ *   gx[b] = Re ifftn( (1 - m_s) G + m_s (|Y| / |X|) (G - u c) )
+ *   gy[j] = sum over the b with perm[b] = j, in the order of b, of Re ifftn( m_s c v )
+ * Where |X(f)| = 0 the tangential term is dropped (its factor is taken as 0); where |Y(f)| = 0 the
+ * coefficient contributes nothing to gy.  gy = NULL skips that gradient, its buffer and its passes
+ * (workspace: with_gy = 0).  lam and M are constants: no gradient with respect to either.
+ *   ws        : >= tb_ampmix_workspace_bytes(plan, B*C, 1, gy != NULL) bytes
+ * Amplitudes are formed as sqrt(re^2 + im^2) in float32: finite while |X|^2 and |Y|^2 stay below FLT_MAX
+ * and above the smallest normal float.  Passes: pass A for every volume of x (of y, of g) before the first
+ * per-coefficient launch -- partners cross launch groups --, one per-coefficient pass and one pass C per
+ * launch group; with gy and perm one ordered sum pass.  Every output element is written exactly once, no
+ * atomics: repeated calls agree bit for bit.  Nothing is allocated, no host sync, launches on `stream` only
+ * (graph-capturable).  TB_ERR_INVALID_ARG for a null pointer (y, perm and gy may be null), B < 1, C < 1,
+ * out_pad < 0 or Cm other than 1 or C; TB_ERR_WORKSPACE for a missing or short workspace; both before any
+ * launch.
+ */
+size_t tb_ampmix_workspace_bytes(const tb_plan* plan, int bc, int with_g, int with_gy);
+int tb_kspace_ampmix_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* y, const int64_t* ys_in,
+                         const int* perm, const float* M, int Cm, const float* lam, float* out, const int64_t* outs,
+                         int out_pad, void* ws, size_t ws_bytes, int B, int C, void* stream);
+int tb_kspace_ampmix_bwd_f32(const tb_plan* plan, const float* x, const int64_t* xs, const float* y,
+                             const int64_t* ys_in, const int* perm, const float* M, int Cm, const float* lam,
+                             const float* g, const int64_t* gs, float* gx, const int64_t* gxs, float* gy,
+                             const int64_t* gys, void* ws, size_t ws_bytes, int B, int C, void* stream);
+
+/*
  * Weight gradient of a 3x3x3 Conv3d / ConvTranspose3d (stride 1 or 2, padding `pad`), f32:
  *   dW[m][c][tz][ty][tx] = sum_n,z,y,x G[n][m][z][y][x] * X[n][c][s z+tz-pad][s y+ty-pad][s x+tx-pad]
  * G [N][M][Do][Ho][Wo] and X [N][Cc][Di][Hi][Wi] contiguous (device); dW [M][Cc][27] (device,

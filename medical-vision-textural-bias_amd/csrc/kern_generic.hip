@@ -252,6 +252,50 @@ __global__ __launch_bounds__(NT_GEN) void k_gen_import(GenSpectrumArgs a) {
   }
 }
 
+// Amplitude mixing (ampmix.h) on full natural-order spectra [bc][H][W][D] indexed by the absolute bc: the
+// closed form of ampmix_unit per coefficient, the mask gathered at s(f) and s(-f).  Every coefficient of the
+// full spectrum is written by its own thread (f and -f evaluate the same expression on conjugate inputs),
+// k_gen_store's real part takes the rest.
+template <bool BWD, bool GY>
+__device__ __forceinline__ void gen_ampmix_body(const AmpMixArgs& a) {
+  const int H = a.pl.H, W = a.pl.W, D = a.pl.D;
+  const int64_t n = (int64_t)H * W * D;
+  const int bc = a.bc0 + (int)blockIdx.y;
+  const int b = bc / a.C, ch = bc - b * a.C;
+  const int ybc = am_partner(a, b) * a.C + ch;
+  const float lam = a.lam[b];
+  const float* __restrict__ Mb = a.M + (a.Cm == 1 ? 0 : (int64_t)ch * n);
+  const cf* Xb = a.Sx + (int64_t)bc * n;
+  const cf* Yb = a.Sy + (int64_t)ybc * n;
+  cf* Ob = a.So + (int64_t)bc * n;
+  for (int64_t e = (int64_t)blockIdx.x * NT_GEN + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT_GEN) {
+    const int64_t hw = e / D;
+    const int kd = (int)(e - hw * D), kh = (int)(hw / W), kw = (int)(hw - (int64_t)kh * W);
+    const float m = lam * mask_factor(Mb[mask_index(0, kh, kw, kd, H, W, D)],
+                                      Mb[mask_index(0, negk(kh, H), negk(kw, W), negk(kd, D), H, W, D)]);
+    if (BWD) {
+      cf gy;
+      Ob[e] = am_mix_bwd<GY>(Xb[e], Yb[e], Ob[e], m, gy);
+      if (GY) a.Sgy[(int64_t)bc * n + e] = gy;
+    } else {
+      Ob[e] = am_mix(Xb[e], Yb[e], m);
+    }
+  }
+}
+__global__ __launch_bounds__(NT_GEN) void k_gen_ampmix(AmpMixArgs) { gen_ampmix_body<false, false>(kargs<AmpMixArgs>()); }
+template <bool GY>
+__global__ __launch_bounds__(NT_GEN) void k_gen_ampmix_bwd(AmpMixArgs) { gen_ampmix_body<true, GY>(kargs<AmpMixArgs>()); }
+
+// out[(j, ch)][e] = sum over the samples b with partner j of Sgy[(b, ch)][e], in the order of b
+__global__ __launch_bounds__(NT_GEN) void k_ampmix_gysum(const cf* __restrict__ Sgy, cf* __restrict__ out,
+                                                         const int* __restrict__ perm, int B, int C, int bc0,
+                                                         int64_t vstride) {
+  const int bc = bc0 + (int)blockIdx.y;
+  const int j = bc / C, ch = bc - j * C;
+  for (int64_t e = (int64_t)blockIdx.x * NT_GEN + threadIdx.x; e < vstride; e += (int64_t)gridDim.x * NT_GEN)
+    out[(int64_t)bc * vstride + e] = am_gysum(Sgy, perm, B, C, j, ch, vstride, e);
+}
+
 unsigned gen_blocks(int64_t n) {
   const int64_t b = (n + NT_GEN * 4 - 1) / (NT_GEN * 4);
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -400,6 +444,74 @@ hipError_t launch_gen_import(const GenLaunch& g, const cf* K, hipStream_t st) {
   if (e != hipSuccess) return e;
   a.S = S0;
   hipLaunchKernelGGL(k_gen_store, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_spectrum_to(const GenLaunch& g, cf* dst, hipStream_t st) {
+  GenArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.pl = g.pl;
+  a.x = g.x;
+  a.xsbc = g.xs[0]; a.xsh = g.xs[1]; a.xsw = g.xs[2];
+  a.S = g.S;
+  a.bc0 = g.bc0;
+  a.C = g.C;
+  a.nbc = g.nbc;
+  const int H = a.pl.H, W = a.pl.W, D = a.pl.D;
+  const int64_t n = (int64_t)H * W * D;
+  cf* tmp = g.S;
+  cf* out = dst + (int64_t)g.bc0 * n;
+  hipLaunchKernelGGL(k_gen_load, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = gen_axis(tmp, out, a.pl.tw[2], D, (int64_t)a.nbc * H * W, 1, false, st);
+  if (e == hipSuccess) e = gen_axis(out, tmp, a.pl.tw[1], W, (int64_t)a.nbc * H, D, false, st);
+  if (e == hipSuccess) e = gen_axis(tmp, out, a.pl.tw[0], H, a.nbc, (int64_t)W * D, false, st);
+  return e;
+}
+
+hipError_t launch_gen_ampmix(const AmpMixArgs& a, int nbc, hipStream_t st) {
+  const int64_t n = (int64_t)a.pl.H * a.pl.W * a.pl.D;
+  hipLaunchKernelGGL(k_gen_ampmix, dim3(gen_blocks(n), nbc), dim3(NT_GEN), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_ampmix_bwd(const AmpMixArgs& a, int nbc, hipStream_t st) {
+  const int64_t n = (int64_t)a.pl.H * a.pl.W * a.pl.D;
+  if (a.need_gy)
+    hipLaunchKernelGGL(k_gen_ampmix_bwd<true>, dim3(gen_blocks(n), nbc), dim3(NT_GEN), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_gen_ampmix_bwd<false>, dim3(gen_blocks(n), nbc), dim3(NT_GEN), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_inverse(const GenLaunch& g, cf* src, hipStream_t st) {
+  GenArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.pl = g.pl;
+  a.y = g.y;
+  a.ysbc = g.ys[0]; a.ysh = g.ys[1]; a.ysw = g.ys[2];
+  a.ypad = g.ypad;
+  a.bc0 = g.bc0;
+  a.C = g.C;
+  a.nbc = g.nbc;
+  a.scale = (float)(1.0 / ((double)g.pl.H * (double)g.pl.W * (double)g.pl.D));
+  const int H = a.pl.H, W = a.pl.W, D = a.pl.D;
+  const int64_t n = (int64_t)H * W * D;
+  cf* in = src + (int64_t)g.bc0 * n;
+  cf* tmp = g.S;
+  hipError_t e = gen_axis(in, tmp, a.pl.tw[0], H, a.nbc, (int64_t)W * D, true, st);
+  if (e == hipSuccess) e = gen_axis(tmp, in, a.pl.tw[1], W, (int64_t)a.nbc * H, D, true, st);
+  if (e == hipSuccess) e = gen_axis(in, tmp, a.pl.tw[2], D, (int64_t)a.nbc * H * W, 1, true, st);
+  if (e != hipSuccess) return e;
+  a.S = tmp;
+  hipLaunchKernelGGL(k_gen_store, dim3(gen_blocks(n), a.nbc), dim3(NT_GEN), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ampmix_gysum(const cf* Sgy, cf* out, const int* perm, int B, int C, int b0, int nb, int64_t vstride,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(k_ampmix_gysum, dim3(gen_blocks(vstride), nb * C), dim3(NT_GEN), 0, st, Sgy, out, perm, B, C,
+                     b0 * C, vstride);
   return hipGetLastError();
 }
 

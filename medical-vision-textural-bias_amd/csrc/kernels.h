@@ -11,6 +11,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "ampmix.h"
 #include "fft_core.h"
 #include "maskgrad.h"
 #include "radial.h"
@@ -77,6 +78,11 @@ template <int RS> hipError_t launch_kspace_maskgrad(const MaskGradArgs& a, dim3 
 template <int RS> hipError_t launch_kspace_export(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
 template <int RS> hipError_t launch_kspace_import(const SpectrumArgs& a, dim3 grid, size_t lds, hipStream_t st);
 
+// amplitude mixing (ampmix.h, kern_ampmix.hip): grid = (tiles of a.T columns, volumes of the launch);
+// a.need_gy picks the backward kernel that also writes Gy
+template <int RS> hipError_t launch_kspace_ampmix(const AmpMixArgs& a, dim3 grid, size_t lds, hipStream_t st);
+template <int RS> hipError_t launch_kspace_ampmix_bwd(const AmpMixArgs& a, dim3 grid, size_t lds, hipStream_t st);
+
 // radial profiles (radial.h, kern_radial.hip).  launch_radial: grid = (units of a.tpg tiles, slots), self picks
 // k_radial_power; launch_radial_sum: the ordered sum of the partials; launch_radial_bin: grid = (units, a.Cm);
 // launch_radial_expand: one element-wise pass
@@ -134,6 +140,19 @@ hipError_t launch_gen_maskgrad(const tb_plan_dev& pl, const cf* X, const cf* G, 
 // inverse axis passes and the store pass, which takes the real part (g.y, g.ys, g.ypad).
 hipError_t launch_gen_export(const GenLaunch& g, cf* K, hipStream_t st);
 hipError_t launch_gen_import(const GenLaunch& g, const cf* K, hipStream_t st);
+// Amplitude mixing on the fallback (ampmix.h), on full spectra [B*C][H][W][D] indexed by the absolute bc.
+// launch_gen_spectrum_to: forward DFT of g.x's nbc volumes from g.bc0 into dst[bc0 ..], scratch (nbc volumes)
+// in g.S.  launch_gen_ampmix / launch_gen_ampmix_bwd: the element-wise closed form of the launch's volumes
+// (a.So: X' out / G in and Gx out; a.Sgy: Gy when a.need_gy).  launch_gen_inverse: inverse DFT of
+// src[bc0 ..] (overwritten) through the scratch g.S and the store pass (g.y, g.ys, g.ypad).
+// launch_ampmix_gysum: out[j] = sum of Sgy[b] over perm[b] = j in the order of b, `vstride` elements per
+// volume, for the volumes of samples [b0, b0 + nb) -- half spectra of the fused route as well.
+hipError_t launch_gen_spectrum_to(const GenLaunch& g, cf* dst, hipStream_t st);
+hipError_t launch_gen_ampmix(const AmpMixArgs& a, int nbc, hipStream_t st);
+hipError_t launch_gen_ampmix_bwd(const AmpMixArgs& a, int nbc, hipStream_t st);
+hipError_t launch_gen_inverse(const GenLaunch& g, cf* src, hipStream_t st);
+hipError_t launch_ampmix_gysum(const cf* Sgy, cf* out, const int* perm, int B, int C, int b0, int nb, int64_t vstride,
+                               hipStream_t st);
 
 #if defined(__HIPCC__)
 struct DevCtx {

@@ -1461,6 +1461,225 @@ int tb_kspace_import_f32(const tb_plan* p, const void* K, float* y, const int64_
 #undef TB_ARGS
 }
 
+// ------------------------------------------------------------ amplitude mixing (ampmix.h)
+// Tiles: the forward's x and partner tiles share one pass-B tile of LDS (half of pass B's width, as the
+// mask gradient); the backward puts the upstream gradient's tile next to them at the same width -- a
+// three-wide tile of at most 48 KB (three workgroups per CU by LDS) -- narrowed where that passes
+// AM_MAX_TILE_BWD coefficients.
+static int ampmix_tile(const tb_plan* p, bool bwd) {
+  int T = pick_tile(p->dev.H, p->lds_max) / 2;
+  if (T < 1) T = 1;
+  const int cap = bwd ? AM_MAX_TILE_BWD / 3 : AM_MAX_TILE / 2;
+  while (T > 1 && p->dev.H * T > cap) --T;
+  while (T > 1 && (size_t)tile_geo(p->dev.H, (bwd ? 3 : 2) * T).total_cf * sizeof(cf) > (size_t)p->lds_max) --T;
+  return T;
+}
+// the element-wise fallback also takes a plan whose single three-wide column exceeds the LDS
+static bool ampmix_generic(const tb_plan* p) {
+  return maskgrad_generic(p) || (size_t)tile_geo(p->dev.H, 3).total_cf * sizeof(cf) > (size_t)p->lds_max;
+}
+
+// Fused route, half spectra of bc volumes each: [S_x][S_y or X'][S_g -> Gx][Gy][sum of Gy over equal partners].
+// Fallback, full spectra: [X][Y][X' or G -> Gx][scratch][Gy][sum of Gy].
+size_t tb_ampmix_workspace_bytes(const tb_plan* plan, int bc, int with_g, int with_gy) {
+  if (!plan || bc < 0) return 0;
+  const int H = plan->dev.H, W = plan->dev.W, D = plan->dev.D;
+  const size_t g = with_g || with_gy ? 1 : 0, gy = with_gy ? 2 : 0;
+  if (ampmix_generic(plan)) return (4 + gy) * (size_t)bc * H * W * D * sizeof(cf);
+  return (2 + g + gy) * (size_t)bc * H * W * (D / 2 + 1) * sizeof(cf);
+}
+
+namespace {
+struct AmpMixCall {
+  const float *x, *y;
+  const int64_t *xs, *ys;
+  const int* perm;
+  const float* M;
+  int Cm;
+  const float* lam;
+  const float* g;     // backward: upstream gradient
+  const int64_t* gs;
+  float* o1;          // forward: out; backward: gx
+  const int64_t* o1s;
+  int o1_pad;
+  float* gy;          // backward: may be null
+  const int64_t* gys;
+};
+}  // namespace
+
+template <int RA>
+static int ampmix_inverse(const tb_plan* p, const cf* S, float* y, const int64_t* ys, int y_pad, int b0, int nb, int C,
+                          hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D;
+  const float scale = (float)(1.0 / ((double)H * (double)W * (double)D));
+  const size_t lds_s = (size_t)slab_geo(W, D).total_cf * sizeof(cf);
+  Timer t(2, st, (double)nb * C * H * W * ((D / 2 + 1) * 8.0 + (D + y_pad) * 4.0), use_ct_slab(p) ? "k_slab_inv_ct" : "k_slab_inv");
+  const SlabInvArgs ia{p->dev, S, y, ys[0], ys[1], ys[2], y_pad, b0 * C, C, scale, nullptr, nb * C};
+  if (use_ct_slab(p))
+    TB_HIP(tb::launch_slab_inv_ct(ia, p->ncu, st));
+  else
+    TB_HIP(launch_slab_inv<RA>(ia, dim3(H, nb * C), lds_s, st));
+  return TB_OK;
+}
+
+template <int RA>
+static int ampmix_forward_all(const tb_plan* p, const float* x, const int64_t* xs, cf* S, int B, int C, hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    Timer t(0, st, (double)nb * C * H * W * (D * 4.0 + Dh * 8.0), use_ct_slab(p) ? "k_slab_fwd_ct16" : "k_slab_fwd");
+    const int rc = launch_slab_fwd<RA>(p, x, xs, S, b0 * C, nb * C, st);
+    if (rc) return rc;
+  }
+  return TB_OK;
+}
+
+// the fallback: full spectra, element-wise closed form, direct-DFT axes
+static int ampmix_gen(const tb_plan* p, const AmpMixCall& c, void* ws, int B, int C, bool bwd, hipStream_t st) {
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D;
+  const size_t nv = (size_t)B * C * H * W * D;
+  cf* X = static_cast<cf*>(ws);
+  cf* Y = c.y ? X + nv : X;
+  cf* O = X + 2 * nv;
+  cf* tmp = X + 3 * nv;
+  cf* Gy = X + 4 * nv;
+  cf* Gys = X + 5 * nv;
+  const double vol = (double)H * W * D;
+  const int nsrc = 1 + (c.y ? 1 : 0) + (bwd ? 1 : 0);
+  for (int s = 0; s < nsrc; ++s) {
+    const bool isg = bwd && s == nsrc - 1;
+    const float* src = isg ? c.g : (s == 0 ? c.x : c.y);
+    const int64_t* ss = isg ? c.gs : (s == 0 ? c.xs : c.ys);
+    cf* dst = isg ? O : (s == 0 ? X : Y);
+    for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+      const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+      Timer t(0, st, nb * C * vol * 60.0, "k_gen_dft");
+      const GenLaunch gl{p->dev, src, ss, nullptr, nullptr, tmp, 0, b0 * C, C, nb * C, nullptr, nullptr};
+      TB_HIP(tb::launch_gen_spectrum_to(gl, dst, st));
+    }
+  }
+  const bool need_gy = bwd && c.gy;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const AmpMixArgs a{p->dev, X, Y, O, Gy, c.M, c.lam, c.perm, C, B, c.Cm, 1, b0 * C, need_gy ? 1 : 0};
+    {
+      Timer t(1, st, nb * C * vol * (bwd ? (need_gy ? 40.0 : 32.0) : 24.0) + c.Cm * vol * 4.0,
+              bwd ? "k_gen_ampmix_bwd" : "k_gen_ampmix");
+      if (bwd)
+        TB_HIP(tb::launch_gen_ampmix_bwd(a, nb * C, st));
+      else
+        TB_HIP(tb::launch_gen_ampmix(a, nb * C, st));
+    }
+    {
+      Timer t(2, st, nb * C * vol * (3.0 * 16.0 + 8.0) + (double)nb * C * H * W * (D + c.o1_pad) * 4.0, "k_gen_dft");
+      const GenLaunch gl{p->dev, nullptr, nullptr, c.o1, c.o1s, tmp, c.o1_pad, b0 * C, C, nb * C, nullptr, nullptr};
+      TB_HIP(tb::launch_gen_inverse(gl, O, st));
+    }
+  }
+  if (!need_gy) return TB_OK;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    if (c.perm) {
+      Timer t(3, st, 2.0 * nb * C * vol * 8.0, "k_ampmix_gysum");
+      TB_HIP(tb::launch_ampmix_gysum(Gy, Gys, c.perm, B, C, b0, nb, (int64_t)H * W * D, st));
+    }
+    Timer t(2, st, nb * C * vol * (3.0 * 16.0 + 8.0 + 4.0), "k_gen_dft");
+    const GenLaunch gl{p->dev, nullptr, nullptr, c.gy, c.gys, tmp, 0, b0 * C, C, nb * C, nullptr, nullptr};
+    TB_HIP(tb::launch_gen_inverse(gl, c.perm ? Gys : Gy, st));
+  }
+  return TB_OK;
+}
+
+template <int RA, int RB>
+static int kspace_ampmix(const tb_plan* p, const AmpMixCall& c, void* ws, int B, int C, bool bwd, hipStream_t st) {
+  if (ampmix_generic(p)) return ampmix_gen(p, c, ws, B, C, bwd, st);
+  const int H = p->dev.H, W = p->dev.W, D = p->dev.D, Dh = D / 2 + 1;
+  const size_t nv = (size_t)B * C * H * W * Dh;
+  const int T = ampmix_tile(p, bwd);
+  const int ntiles = (W * Dh + T - 1) / T;
+  const size_t lds = (size_t)tile_geo(H, (bwd ? 3 : 2) * T).total_cf * sizeof(cf);
+  cf* Sx = static_cast<cf*>(ws);
+  cf* S2 = Sx + nv;
+  cf* Sg = Sx + 2 * nv;
+  cf* Sgy = Sx + 3 * nv;
+  cf* Sgys = Sx + 4 * nv;
+  // partners cross launch groups: every forward pass runs before the first per-coefficient launch
+  int rc = ampmix_forward_all<RA>(p, c.x, c.xs, Sx, B, C, st);
+  if (rc) return rc;
+  if (c.y) {
+    rc = ampmix_forward_all<RA>(p, c.y, c.ys, S2, B, C, st);
+    if (rc) return rc;
+  }
+  if (bwd) {
+    rc = ampmix_forward_all<RA>(p, c.g, c.gs, Sg, B, C, st);
+    if (rc) return rc;
+  }
+  const cf* Sy = c.y ? S2 : Sx;
+  // forward: X' over S_x when the partners have their own buffer, else into the second one
+  cf* So = bwd ? Sg : (c.y ? Sx : S2);
+  const bool need_gy = bwd && c.gy;
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    const double spec = (double)nb * C * H * W * Dh * 8.0;
+    {
+      Timer t(1, st, (bwd ? (need_gy ? 5.0 : 4.0) : 3.0) * spec + (double)c.Cm * H * W * D * 4.0,
+              bwd ? "k_kspace_ampmix_bwd" : "k_kspace_ampmix");
+      const AmpMixArgs a{p->dev, Sx, Sy, So, Sgy, c.M, c.lam, c.perm, C, B, c.Cm, T, b0 * C, need_gy ? 1 : 0};
+      if (bwd)
+        TB_HIP(launch_kspace_ampmix_bwd<RB>(a, dim3(ntiles, nb * C), lds, st));
+      else
+        TB_HIP(launch_kspace_ampmix<RB>(a, dim3(ntiles, nb * C), lds, st));
+    }
+    rc = ampmix_inverse<RA>(p, So, c.o1, c.o1s, c.o1_pad, b0, nb, C, st);
+    if (rc) return rc;
+  }
+  if (!need_gy) return TB_OK;
+  // Gy of sample b belongs to row perm[b] of y: summed over equal partners in the order of b, on the
+  // half spectra (the inverse is linear), then one pass C
+  for (int b0 = 0; b0 < B; b0 += TB_MAX_BATCH) {
+    const int nb = (B - b0) < TB_MAX_BATCH ? (B - b0) : TB_MAX_BATCH;
+    if (c.perm) {
+      Timer t(3, st, 2.0 * (double)nb * C * H * W * Dh * 8.0, "k_ampmix_gysum");
+      TB_HIP(tb::launch_ampmix_gysum(Sgy, Sgys, c.perm, B, C, b0, nb, (int64_t)H * W * Dh, st));
+    }
+    rc = ampmix_inverse<RA>(p, c.perm ? Sgys : Sgy, c.gy, c.gys, 0, b0, nb, C, st);
+    if (rc) return rc;
+  }
+  return TB_OK;
+}
+
+static int ampmix_entry(const tb_plan* p, const AmpMixCall& c, void* ws, int B, int C, bool bwd, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define TB_ARGS p, c, ws, B, C, bwd, st
+  if (p->rset_wd == RS_SMALL)
+    return p->rset_h == RS_SMALL ? kspace_ampmix<RS_SMALL, RS_SMALL>(TB_ARGS) : kspace_ampmix<RS_SMALL, RS_ALL>(TB_ARGS);
+  return p->rset_h == RS_SMALL ? kspace_ampmix<RS_ALL, RS_SMALL>(TB_ARGS) : kspace_ampmix<RS_ALL, RS_ALL>(TB_ARGS);
+#undef TB_ARGS
+}
+
+int tb_kspace_ampmix_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* y, const int64_t* ys_in,
+                         const int* perm, const float* M, int Cm, const float* lam, float* out, const int64_t* outs,
+                         int out_pad, void* ws, size_t ws_bytes, int B, int C, void* stream) {
+  if (!p || !x || !xs || (y && !ys_in) || !M || !lam || !out || !outs || out_pad < 0 || B < 1 || C < 1 ||
+      (Cm != 1 && Cm != C))
+    return TB_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < tb_ampmix_workspace_bytes(p, B * C, 0, 0)) return TB_ERR_WORKSPACE;
+  const AmpMixCall c{x, y, xs, ys_in, perm, M, Cm, lam, nullptr, nullptr, out, outs, out_pad, nullptr, nullptr};
+  return ampmix_entry(p, c, ws, B, C, false, stream);
+}
+
+int tb_kspace_ampmix_bwd_f32(const tb_plan* p, const float* x, const int64_t* xs, const float* y, const int64_t* ys_in,
+                             const int* perm, const float* M, int Cm, const float* lam, const float* g,
+                             const int64_t* gs, float* gx, const int64_t* gxs, float* gy, const int64_t* gys, void* ws,
+                             size_t ws_bytes, int B, int C, void* stream) {
+  if (!p || !x || !xs || (y && !ys_in) || !M || !lam || !g || !gs || !gx || !gxs || (gy && !gys) || B < 1 || C < 1 ||
+      (Cm != 1 && Cm != C))
+    return TB_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < tb_ampmix_workspace_bytes(p, B * C, 1, gy ? 1 : 0)) return TB_ERR_WORKSPACE;
+  const AmpMixCall c{x, y, xs, ys_in, perm, M, Cm, lam, g, gs, gx, gxs, 0, gy, gys};
+  return ampmix_entry(p, c, ws, B, C, true, stream);
+}
+
 int tb_kspace_filter_f32(const tb_plan* p, const float* x, const int64_t* xs, float* y, const int64_t* ys, int y_pad,
                          void* ws, size_t ws_bytes, int B, int C, const tb_sample_ops* ops, uint32_t* minmax,
                          void* stream) {

@@ -13,6 +13,8 @@ Layering (DESIGN.md):
                      RadialFilterd and the trainable LearnedRadialFilter
   spikes             the trainable spike layer (LearnedSpikeLayer): device-resident log-intensities with
                      closed-form gradients with respect to them and to the image
+  amplitude          amplitude mixing in k-space (Fourier domain adaptation): amplitude_mix, lowfreq_box,
+                     AmplitudeMix and the batch stage RandAmplitudeMix, fused, with gradients for both images
   pipeline           batched device-side augmentation stage (fused chain) for training
   unet / losses      MONAI-equivalent 3-D residual U-Net and DiceLoss (PyTorch-ROCm)
   train              train step, DDP over RCCL
@@ -31,8 +33,9 @@ for _d in ("FWD", "BWD", "WRW"):
 
 
 def __getattr__(name):
-    # texbias.spectrum / texbias.radial / texbias.spikes without importing torch at package import
-    if name in ("spectrum", "radial", "spikes"):
+    # texbias.spectrum / texbias.radial / texbias.spikes / texbias.amplitude without importing torch at
+    # package import
+    if name in ("spectrum", "radial", "spikes", "amplitude"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -55,6 +55,9 @@ def _proto(L):
         "tb_spectrum_workspace_bytes": (SZ, [P, I]),
         "tb_kspace_export_f32": (I, [P, P, P, P, P, SZ, I, I, P]),
         "tb_kspace_import_f32": (I, [P, P, P, P, I, P, SZ, I, I, P]),
+        "tb_ampmix_workspace_bytes": (SZ, [P, I, I, I]),
+        "tb_kspace_ampmix_f32": (I, [P, P, P, P, P, P, P, I, P, P, P, I, P, SZ, I, I, P]),
+        "tb_kspace_ampmix_bwd_f32": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, SZ, I, I, P]),
         "tb_conv3d_wgrad_f32": (I, [P, P, P] + [I] * 11 + [P]),
         "tb_conv3d_wgrad_config": (I, [I] * 11 + [P]),
         "tb_conv3d_wgrad_plan": (I, [I] * 11 + [P]),

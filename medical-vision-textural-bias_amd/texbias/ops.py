@@ -35,11 +35,15 @@ Reference interfaces each op replaces (file:line under the reference root):
                              w.r.t. the image and the log-intensity in closed form (the reference's drivers update
                              it by finite differences, spikes11_layer_domain_GD.py:260-275)
   texbias::kspace_spikes_grad   the two gradients on their own
+  texbias::amp_mix           what a user of Fourier.shift_fourier / inv_shift_fourier (:594-632) composes by hand
+                             for amplitude mixing (abs, angle, polar between the two): the phase of x with the
+                             amplitude moved towards a partner's, fused, with autograd w.r.t. both images
+  texbias::amp_mix_grad      its two gradients on their own
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -542,6 +546,68 @@ def _kspace_spikes_backward(ctx, gy, gcoef):
 
 
 kspace_spikes.register_autograd(_kspace_spikes_backward, setup_context=_kspace_spikes_setup)
+
+
+# amplitude mixing (csrc/ampmix.h): the phase of x's spectrum with an amplitude moved towards a partner's
+@torch.library.custom_op("texbias::amp_mix", mutates_args=())
+def amp_mix(x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, lam: torch.Tensor, perm: Optional[torch.Tensor],
+            n_dims: int, channels: int, pad: int = 0) -> torch.Tensor:
+    """out[b] = Re(ifftn(ifftshift(polar((1 - m) |X| + m |Y|, angle(X))))) over the trailing ``n_dims`` axes of
+    [B, channels, *spatial], X = fftshift(fftn(x[b])), Y = fftshift(fftn(y[perm[b]])), m = lam[b] * mask:
+    ``mask`` as in ``kspace_mask`` (``spatial`` or ``(channels,) + spatial``), ``lam`` float32 [B] and ``perm``
+    int32 [B] (or None: identity) on x's device, read by the kernel on the current stream.  ``y`` may be ``x``
+    itself: the partners are then rows of x and only one set of forward passes runs.  Autograd with respect
+    to ``x`` and ``y``; ``lam`` and ``mask`` are constants (their gradients are None)."""
+    return rt.kspace_ampmix(x, y, mask, lam, perm, n_dims, channels, pad)
+
+
+@amp_mix.register_fake
+def _amp_mix_fake(x, y, mask, lam, perm, n_dims, channels, pad=0):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+
+
+@torch.library.custom_op("texbias::amp_mix_grad", mutates_args=())
+def amp_mix_grad(x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, lam: torch.Tensor,
+                 perm: Optional[torch.Tensor], g: torch.Tensor, n_dims: int, channels: int,
+                 need_gy: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gradients of ``amp_mix`` with respect to ``x`` and ``y`` for the upstream gradient ``g`` (x's shape,
+    any strides with a contiguous last axis): (gx, gy); gy summed over equal partners in a fixed order.
+    ``need_gy`` False: the partner's gradient is neither computed nor stored and gy is an empty tensor.  No
+    autograd formula (double backward is not supported)."""
+    gx, gy = rt.kspace_ampmix_grad(x, y, mask, lam, perm, g, n_dims, channels, need_gy)
+    return gx, (gy if need_gy else g.new_empty((0,)))
+
+
+@amp_mix_grad.register_fake
+def _amp_mix_grad_fake(x, y, mask, lam, perm, g, n_dims, channels, need_gy):
+    return x.new_empty(x.shape), x.new_empty(x.shape if need_gy else (0,))
+
+
+def _amp_mix_setup(ctx, inputs, output):
+    x, y, mask, lam, perm, n_dims, channels, pad = inputs
+    if mask.requires_grad or lam.requires_grad:
+        raise ValueError("texbias::amp_mix has no gradient w.r.t. the mask or lam (both are constants)")
+    ctx.save_for_backward(x, y, mask, lam, perm)
+    ctx.n_dims, ctx.channels, ctx.d = n_dims, channels, x.shape[-1]
+
+
+@torch.autograd.function.once_differentiable
+def _amp_mix_backward(ctx, go):
+    # closed form per coefficient (csrc/ampmix.h); the partner's share only when y requires grad; the zero pad
+    # columns take no gradient, and the view without them is read in place.  When y is x, autograd adds the
+    # two returned gradients into the one leaf.
+    x, y, mask, lam, perm = ctx.saved_tensors
+    gx = gy = None
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        need_gy = bool(ctx.needs_input_grad[1])
+        rx, ry = torch.ops.texbias.amp_mix_grad(x, y, mask, lam, perm, go[..., : ctx.d], ctx.n_dims, ctx.channels,
+                                                need_gy)
+        gx = rx if ctx.needs_input_grad[0] else None
+        gy = ry if need_gy else None
+    return gx, gy, None, None, None, None, None, None
+
+
+amp_mix.register_autograd(_amp_mix_backward, setup_context=_amp_mix_setup)
 
 
 def _layer_apply(img: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

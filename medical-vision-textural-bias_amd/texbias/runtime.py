@@ -507,6 +507,132 @@ def kspace_import(k: torch.Tensor, n_dims: int, pad: int = 0, out: Optional[torc
     return y
 
 
+# ------------------------------------------------------------------ amplitude mixing (tb_kspace_ampmix_*, csrc/ampmix.h)
+def _ampmix_args(what, x, y, mask, lam, perm, n_dims, channels):
+    """Host-side check of the arguments of amplitude mixing: (x, xs, y or None, ys, mask channels, channels,
+    samples, geometry).  ``y`` that is ``x`` (the same storage, shape and strides) comes back as None: the
+    partners are then rows of x and only one set of forward passes runs."""
+    if not isinstance(y, torch.Tensor):
+        raise ValueError(f"{what}: image and partner must be torch tensors")
+    cm, channels = _mask_geometry(what, torch.float32, x, mask, n_dims, channels, False)
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f"{what}: partner {tuple(y.shape)} does not match the image {tuple(x.shape)}")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError(f"{what}: float32 tensors expected, got {x.dtype} and {y.dtype}")
+    if y.device != x.device:
+        raise ValueError(f"{what}: partner on {y.device}, image on {x.device}")
+    lead = x.shape[: x.dim() - n_dims]
+    bc = int(np.prod(lead)) if len(lead) else 1
+    B = bc // channels
+    if not isinstance(lam, torch.Tensor) or lam.dtype != torch.float32 or tuple(lam.shape) != (B,) \
+            or not lam.is_contiguous():
+        raise ValueError(f"{what}: lam must be a float32 contiguous [{B}] tensor (one strength per sample)")
+    if perm is not None and (not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32
+                             or tuple(perm.shape) != (B,) or not perm.is_contiguous()):
+        raise ValueError(f"{what}: perm must be None or an int32 contiguous [{B}] tensor (one partner per sample)")
+    for name, t in (("lam", lam), ("perm", perm)):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{what}: {name} on {t.device}, image on {x.device} (both are read by the kernel)")
+    require_hip(x, what)
+    geo = geometry(tuple(x.shape[x.dim() - n_dims:]))
+    same = y is x or (y.data_ptr() == x.data_ptr() and y.stride() == x.stride())
+
+    def strided(t):
+        s = _image_strides(t, n_dims, geo)
+        if s is None:
+            t = t.contiguous()
+            s = _image_strides(t, n_dims, geo)
+        return t, s
+
+    x, xs = strided(x)
+    if same:
+        return x, xs, None, None, cm, channels, B, geo
+    y, ys = strided(y)
+    return x, xs, y, ys, cm, channels, B, geo
+
+
+def kspace_ampmix(x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, lam: torch.Tensor,
+                  perm: Optional[torch.Tensor], n_dims: int, channels: Optional[int] = None, pad: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Amplitude mixing over the trailing ``n_dims`` axes of ``x`` [B, C, *spatial]: sample b keeps the phase of
+    its spectrum and takes the amplitude (1 - m) |X| + m |Y| with Y the spectrum of ``y[perm[b]]`` and
+    m = ``lam[b]`` * ``mask`` (``mask`` as in ``kspace_mask``; ``lam`` float32 [B] and ``perm`` int32 [B] or
+    None on x's device, read by the kernel on the current stream -- no host read).  ``y`` may be ``x``
+    itself (batch-internal mixing, one set of forward passes).  ``perm`` values outside [0, B) are clamped
+    by the kernel; the caller owes a valid index.  ``pad`` / ``out`` as ``kspace_import``.  No spectrum is
+    stored outside the workspace (``tb_kspace_ampmix_f32``)."""
+    what = "kspace_ampmix"
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{what}: image and partner must be torch tensors")
+    x, xs, y, ys, cm, channels, B, geo = _ampmix_args(what, x, y, mask, lam, perm, n_dims, channels)
+    H, W, D = geo.hwd
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError(f"{what}: pad must be >= 0, got {pad}")
+    if pad and len(geo.kept) and geo.kept[-1] != n_dims - 1:
+        raise ValueError(f"{what}: padding requires a non-singleton last axis")
+    shape = tuple(x.shape[:-1]) + (x.shape[-1] + pad,)
+    if out is None:
+        o = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        o = out
+        if not isinstance(o, torch.Tensor) or tuple(o.shape) != shape or o.dtype != torch.float32 or o.device != x.device:
+            raise ValueError(f"{what}: out must be a float32 {shape} tensor on {x.device}")
+    os_ = _image_strides(o, n_dims, geo)
+    if os_ is None:
+        raise ValueError(f"{what}: out must collapse its leading axes and have a contiguous last axis")
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_ampmix_workspace_bytes(plan.handle, B * channels, 0, 0)))
+        check(lib().tb_kspace_ampmix_f32(plan.handle, x.data_ptr(), xs, None if y is None else y.data_ptr(), ys,
+                                         None if perm is None else perm.data_ptr(), mask.data_ptr(), cm,
+                                         lam.data_ptr(), o.data_ptr(), os_, pad, ws.data_ptr(), ws.numel(), B, channels,
+                                         _stream(x.device)), "tb_kspace_ampmix_f32")
+    return o
+
+
+def ampmix_workspace_bytes(x: torch.Tensor, n_dims: int, with_g: bool, with_gy: bool) -> int:
+    """Workspace bytes of amplitude mixing for the volumes of ``x`` [*lead, *spatial]: the forward
+    (``with_g`` False), the gradient with respect to x, and with ``with_gy`` also to y."""
+    geo, bc = _spectrum_args("ampmix_workspace_bytes", x, n_dims, torch.float32)
+    plan = plan_for(x.device, *geo.hwd)
+    return int(lib().tb_ampmix_workspace_bytes(plan.handle, bc, 1 if with_g else 0, 1 if with_gy else 0))
+
+
+def kspace_ampmix_grad(x: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, lam: torch.Tensor,
+                       perm: Optional[torch.Tensor], g: torch.Tensor, n_dims: int, channels: Optional[int] = None,
+                       need_gy: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Gradients of ``kspace_ampmix`` with respect to ``x`` and ``y`` for the upstream gradient ``g`` (x's shape,
+    any strides with a contiguous last axis): (gx, gy), both of x's shape.  gy[j] is the sum over the samples
+    b with ``perm[b]`` = j in the order of b (no atomics: repeated calls agree bit for bit); with ``need_gy``
+    False it is None, and neither its buffer nor its passes exist.  When ``y`` is ``x`` the two are still
+    returned apart: the gradient of the batch-internal mix is their sum.  Where |X(f)| = 0 the tangential term
+    of gx is dropped, where |Y(f)| = 0 the coefficient adds nothing to gy (``tb_kspace_ampmix_bwd_f32``)."""
+    what = "kspace_ampmix_grad"
+    if not isinstance(x, torch.Tensor) or not isinstance(g, torch.Tensor):
+        raise ValueError(f"{what}: image and upstream gradient must be torch tensors")
+    if tuple(g.shape) != tuple(x.shape) or g.dtype != torch.float32 or g.device != x.device:
+        raise ValueError(f"{what}: the upstream gradient must be a float32 {tuple(x.shape)} tensor on {x.device}")
+    x, xs, y, ys, cm, channels, B, geo = _ampmix_args(what, x, y, mask, lam, perm, n_dims, channels)
+    H, W, D = geo.hwd
+    gs = _image_strides(g, n_dims, geo)
+    if gs is None:
+        g = g.contiguous()
+        gs = _image_strides(g, n_dims, geo)
+    gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    gy = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_gy else None
+    gxs = _image_strides(gx, n_dims, geo)
+    plan = plan_for(x.device, H, W, D)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, int(lib().tb_ampmix_workspace_bytes(plan.handle, B * channels, 1, 1 if need_gy else 0)))
+        check(lib().tb_kspace_ampmix_bwd_f32(plan.handle, x.data_ptr(), xs, None if y is None else y.data_ptr(), ys,
+                                             None if perm is None else perm.data_ptr(), mask.data_ptr(), cm,
+                                             lam.data_ptr(), g.data_ptr(), gs, gx.data_ptr(), gxs,
+                                             None if gy is None else gy.data_ptr(), gxs, ws.data_ptr(), ws.numel(), B,
+                                             channels, _stream(x.device)), "tb_kspace_ampmix_bwd_f32")
+    return gx, gy
+
+
 # ------------------------------------------------------------------ radial profiles (tb_radial_*, csrc/radial.h)
 RADIAL_MODES = {"nearest": 0, "linear": 1}
 RADIAL_MAX_BINS = 2048
