@@ -587,6 +587,31 @@ int tb_conv3d_gemm_f32(int mode, const float* x, int64_t xsn, const float* W, co
 int tb_conv3d_gemm_config(int mode, int N, int Cin, int M, int D, int H, int Wd, int stride, int ksize, int64_t* cfg);
 
 /*
+ * ConvTranspose3d(Cin -> Cout, 3, stride 2, padding 1, output_padding 1) forward for Cout = 32 or 64 and Cin a
+ * multiple of 32, in split precision on the bf16 matrix cores with the eight sub-pixel classes stacked over one
+ * gather (csrc/conv_stack.hip; the U-Net's up2 128 -> 32 and up3 384 -> 64 of the reference's MONAI UNet,
+ * 10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-199).  x [N][Cin][Di][Hi][Wi] contiguous, W [Cin][Cout][27]
+ * as the module holds it, bias [Cout] or NULL, y [N][Cout][2Di][2Hi][2Wi] with samples y_sn floats apart, add (or
+ * NULL; y's layout within a sample, samples add_sn apart) summed into the store; 0 strides: contiguous; otherwise
+ * each may be a channel slice of a wider tensor (even strides, y and add 8-B aligned).  With a stride-2
+ * Conv3d(Cout -> Cin)'s weight [Cin][Cout][27] it is that layer's input gradient (x = dY, y = dX).  Other channel
+ * counts and tensors past 2 GiB return TB_ERR_UNSUPPORTED_SIZE.  ws: device scratch of tb_convT3d_stack_ws_bytes
+ * (packed weights, the k slices' partials; stream-ordered reuse; 0: no plan).  No float atomics.
+ * tb_convT3d_stack_config: cfg[0..7] = positions per block, k slices, channel blocks per slice, blocks, positions,
+ * partial bytes, packed-weight bytes, workspace bytes (host only).  tb_convT3d_stack_pack_index: the element index
+ * of W[c][m][tap] in a packed part image and the (class 4 pz + 2 py + px, neighbour offset 4 dz + 2 dy + dx) pair
+ * the tap belongs to (host only).  tb_convT3d_stack_set_split(n > 0) forces n k slices (measurement, tests; 0: the
+ * plan's choice).
+ */
+size_t tb_convT3d_stack_ws_bytes(int N, int Cin, int Cout, int Di, int Hi, int Wi);
+int tb_convT3d_stack_config(int N, int Cin, int Cout, int Di, int Hi, int Wi, int64_t* cfg);
+int tb_convT3d_stack_pack_index(int Cin, int Cout, int c, int m, int tap, int64_t* index, int* cls, int* offset);
+int tb_convT3d_stack_set_split(int slices);
+int tb_convT3d_stack_f32(const float* x, const float* W, const float* bias, const float* add, int64_t add_sn, float* y,
+                         int64_t y_sn, int N, int Cin, int Cout, int Di, int Hi, int Wi, void* ws, size_t ws_bytes,
+                         void* stream);
+
+/*
  * The weight gradient of the U-Net's deepest levels as one implicit GEMM on the f32 matrix cores
  * (csrc/conv_wgrad_gemm.hip; train step of 10_scripts/20_Gibbs_filters/stylized_gibbs12p5.py:192-243, MONAI
  * UNet module tree source_code/test.ipynb:754-1010 -- the 15 x 15 x 10 level at the C3 shape: the stride-2

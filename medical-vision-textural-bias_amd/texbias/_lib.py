@@ -92,6 +92,11 @@ def _proto(L):
         "tb_conv3d_gemm_workspace_bytes": (SZ, [I] * 9),
         "tb_conv3d_gemm_f32": (I, [I, P, I64, P, P, P, I64, P, I64] + [I] * 8 + [P, SZ, P]),
         "tb_conv3d_gemm_config": (I, [I] * 9 + [P]),
+        "tb_convT3d_stack_ws_bytes": (SZ, [I] * 6),
+        "tb_convT3d_stack_config": (I, [I] * 6 + [P]),
+        "tb_convT3d_stack_pack_index": (I, [I] * 5 + [P, P, P]),
+        "tb_convT3d_stack_set_split": (I, [I]),
+        "tb_convT3d_stack_f32": (I, [P, P, P, P, I64, P, I64] + [I] * 6 + [P, SZ, P]),
         "tb_conv3d_wgrad_gemm_ws_bytes": (SZ, [I] * 11),
         "tb_conv3d_wgrad_gemm_f32": (I, [P, I64, P, I64, P] + [I] * 11 + [P, SZ, P]),
         "tb_conv3d_wgrad_gemm_config": (I, [I] * 11 + [P]),

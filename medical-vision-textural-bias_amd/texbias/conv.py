@@ -476,6 +476,84 @@ def convT_mfma(x: torch.Tensor, w: torch.Tensor, b, add=None, out=None) -> torch
 convT_mfma64 = convT_mfma
 
 
+# ---------------------------------------------------------------- deep transposed convs, classes stacked
+# ConvTranspose3d(Cin -> 32 / 64) forwards and the input gradients of the stacked stride-2 units on
+# k_convT_stack (csrc/conv_stack.hip); False leaves them on MIOpen / CK (col2im, bwd-data, layout transposes).
+CONVT_STACK = True
+# the stacked unit's input gradient plus the skip share in that kernel's store (as CONVT_DX_ADD one level up).
+# Off: at C3 (32 -> 128 stacked, 30 x 30 x 20) the call with `add` in the store is 165.4 us (162.8 - 168.1) against
+# 170.5 us (166.2 - 177.3) for kernel + torch.add: 5 us, under three spreads (26 us); at 64 -> 256 the kernel is not
+# routed at all (profiles/r25/README.md §3).
+CONVT_STACK_DX_ADD = False
+# Gate, per direction: (Cin, Cout) -> least positions per sample (Di Hi Wi of the product's input grid) from
+# which the call goes to the kernel; a pair that is not listed stays on ATen.  Isolated medians, us, batch 2, caches
+# flushed, three alternating processes per arm, (min - max) over all of them (profiles/r25/README.md §3):
+#   forward 128 -> 32 at 30 x 30 x 20:        ATen 234.0 (229.8 - 238.1), kernel 150.7 (146.8 - 153.2): routed;
+#   input gradient 128 -> 32 at 30 x 30 x 20: ATen 219.6 (215.7 - 222.4), kernel 147.8 (145.7 - 152.8): routed;
+#   forward 384 -> 64 at 15 x 15 x 10:        ATen 121.8 (119.8 - 123.8), kernel 124.8 (3 slices) / 150.2 (1): ATen;
+#   input gradient 256 -> 64 at 15 x 15 x 10: ATen 100.0 (98.7 - 103.5), kernel 104.4 (1 slice) / 99.9 (3): ATen.
+# Nothing was measured below 18 000 positions for 128 -> 32.
+CONVT_STACK_FWD_MIN_POS = {(128, 32): 18000}
+CONVT_STACK_DX_MIN_POS = {(128, 32): 18000}
+
+
+@functools.lru_cache(maxsize=256)
+def _cts_ws_bytes(N, Cin, Cout, D, H, W) -> int:
+    return int(lib().tb_convT3d_stack_ws_bytes(N, Cin, Cout, D, H, W))
+
+
+def convT_stack_config(x_shape, cout: int):
+    """The plan of ``convT_stack`` for x [N, Cin, Di, Hi, Wi] -> Cout (host only, tb_convT3d_stack_config):
+    BP, nsplit, cper, blocks, positions, part_bytes, pack_bytes, ws_bytes -- or None when the entry refuses."""
+    cfg = (ctypes.c_int64 * 8)()
+    N, Cin, D, H, W = x_shape
+    if lib().tb_convT3d_stack_config(N, Cin, cout, D, H, W, cfg) != 0:
+        return None
+    return dict(zip(("BP", "nsplit", "cper", "blocks", "positions", "part_bytes", "pack_bytes", "ws_bytes"), list(cfg)))
+
+
+def convT_stack_rc(x: torch.Tensor, w: torch.Tensor, b, add=None, out=None):
+    """(return code, y) of tb_convT3d_stack_f32: ConvTranspose3d(Cin -> Cout = 32 / 64, 3, stride 2, padding 1,
+    output_padding 1) of x with w [Cin, Cout, 3, 3, 3] -- a ConvTranspose3d's weight, or a stride-2
+    Conv3d(Cout -> Cin)'s, whose input gradient this then is.  ``add`` is summed into the store, ``out`` receives
+    the result; each may be a channel slice of a wider tensor."""
+    x = x.contiguous()
+    w = w.contiguous()
+    N, Cin, D, H, W = x.shape
+    Cout = w.shape[1]
+    shape = (N, Cout, 2 * D, 2 * H, 2 * W)
+    y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    ysn = _sample_stride(y, shape)
+    assert ysn > 0 and ysn % 2 == 0 and y.data_ptr() % 8 == 0, "out: the output's shape, samples contiguous"
+    asn = 0
+    if add is not None:
+        asn = _sample_stride(add, shape)
+        if asn <= 0 or asn % 2 or add.data_ptr() % 8:
+            add = add.contiguous()
+            asn = add.stride(0)
+    nb = _cts_ws_bytes(N, Cin, Cout, D, H, W)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib().tb_convT3d_stack_f32(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
+                                        add.data_ptr() if add is not None else None, asn, y.data_ptr(), ysn,
+                                        N, Cin, Cout, D, H, W, ws.data_ptr(), nb, _stream(x))
+    return rc, y
+
+
+def convT_stack(x: torch.Tensor, w: torch.Tensor, b, add=None, out=None) -> torch.Tensor:
+    rc, y = convT_stack_rc(x, w, b, add, out)
+    check(rc, "tb_convT3d_stack_f32")
+    return y
+
+
+def convT_stack_applies(N: int, Cin: int, Cout: int, spatial, gate: dict) -> bool:
+    """The product ConvTranspose3d(Cin -> Cout) on the input grid ``spatial`` goes to ``convT_stack``: the
+    switch, the direction's measured gate, and a plan in the library."""
+    lim = gate.get((Cin, Cout))
+    return CONVT_STACK and lim is not None and math.prod(spatial) >= lim and Cout in (32, 64) and Cin % 32 == 0 and \
+        _cts_ws_bytes(N, Cin, Cout, *spatial) > 0
+
+
 def s2_dgrad_applies(gy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, stride, padding) -> bool:
     """Conv3d(16 -> 32, 3, stride 2, padding 1) on even extents: its input gradient is
     conv_transpose3d(dY, W) with output_padding 1, i.e. k_convT_mfma64 with 32 input channels."""
@@ -637,7 +715,8 @@ class Route:
     bias gradient -- chosen once from the shapes (the gates above), so that the layer's autograd function
     and the fused U-Net blocks (``texbias.unet``) share one dispatch.  Kinds: ``fwd16`` (k_conv3d_fwd16),
     ``mfma`` (k_conv3d_mfma_s1), ``fewin`` (k_conv_s2_fewin), ``small`` (k_conv3d_small_z), ``fewout``
-    (k_convT_fewout), ``convT64`` (k_convT_split / k_convT_mfma64), ``gemm`` (k_conv_gemm), ``aten`` (MIOpen / CK)."""
+    (k_convT_fewout), ``convT64`` (k_convT_split / k_convT_mfma64), ``convTs`` (k_convT_stack), ``gemm``
+    (k_conv_gemm), ``aten`` (MIOpen / CK)."""
 
     __slots__ = ("kind", "dx", "stride", "padding", "output_padding", "transposed", "fast_w", "k", "wgg")
 
@@ -651,6 +730,10 @@ class Route:
         elif transposed:
             self.kind = ("fewout" if convT_fewout_applies(x, w, st, pd, op) else
                          "convT64" if convT64_applies(x, w, st, pd, op) else
+                         "convTs" if (tuple(w.shape[2:]) == (3, 3, 3) and st == (2, 2, 2) and pd == (1, 1, 1) and
+                                      op == (1, 1, 1) and x.dim() == 5 and x.shape[1] == w.shape[0] and
+                                      convT_stack_applies(x.shape[0], w.shape[0], w.shape[1], x.shape[2:],
+                                                          CONVT_STACK_FWD_MIN_POS)) else
                          "gemm" if gemm_applies(x, w, st, pd, True, op) else "aten")
         else:
             self.kind = ("fwd16" if conv16_applies(x, w, st, pd) else
@@ -668,7 +751,12 @@ class Route:
                     and CONVT64 and x.shape[-1] % 8 == 0 and x.shape[-1] // 2 <= 64 and \
                     all(n % 2 == 0 for n in x.shape[2:]):
                 self.dx = "convT64"   # Conv3d(16 -> 32 / 64 stacked, s2)'s input gradient on k_convT_mfma64
-            elif (self.kind != "aten" or (transposed and GEMM_TDX)) and _gemm_geom_ok(x, w, st, pd, transposed, op) and \
+            elif not transposed and custom_backward_applies(x, w) and tuple(w.shape[2:]) == (3, 3, 3) and st == (2, 2, 2) and pd == (1, 1, 1) and \
+                    x.dim() == 5 and x.shape[1] == w.shape[1] and all(n % 2 == 0 for n in x.shape[2:]) and \
+                    convT_stack_applies(x.shape[0], w.shape[0], w.shape[1], [n // 2 for n in x.shape[2:]],
+                                        CONVT_STACK_DX_MIN_POS):
+                self.dx = "convTs"    # Conv3d(32 / 64 -> stacked, s2)'s input gradient on k_convT_stack
+            elif (self.kind not in ("aten", "convTs") or (transposed and GEMM_TDX)) and _gemm_geom_ok(x, w, st, pd, transposed, op) and \
                     (w.shape[1] % 8 == 0 if transposed else w.shape[0] % 8 == 0) and \
                     (transposed or st[0] == 1 or (GEMM_T and all(n % 2 == 0 for n in x.shape[2:]))):
                 # ConvTranspose3d: a stride-2 Conv3d of dY (the GEMM's conv form); stride-1 Conv3d: the
@@ -712,6 +800,8 @@ class Route:
             return convT_fewout(x, w, b)
         if k == "convT64":
             return convT_mfma(x, w, b)
+        if k == "convTs":
+            return convT_stack(x, w, b)
         if k == "gemm":
             return conv_gemm(x, w, b, "convT" if self.transposed else "conv", self.stride[0], self.k)
         if self.transposed:
@@ -720,12 +810,17 @@ class Route:
 
     # -- input gradient (x only for its shape on the ATen path; ``add`` summed in, as in forward)
     def input_grad(self, gy, x, w, add=None, out=None):
-        """``out`` (the ``convT64`` kernel only): where the result goes, a channel slice of a wider tensor."""
+        """``out`` (the ``convT64`` and ``convTs`` kernels only): where the result goes, a channel slice of a wider
+        tensor."""
         k = self.dx
         if out is not None:
-            assert k == "convT64"
+            assert k in ("convT64", "convTs")
+            if k == "convTs":
+                return convT_stack(gy, w, None, add=add, out=out)
             return convT_mfma(gy if gy.data_ptr() % 16 == 0 else gy.clone(), w, None, add=add, out=out)
         if add is not None:  # (a strided add -- a channel slice of the skip concatenation's gradient -- is
+            if k == "convTs" and CONVT_STACK_DX_ADD:
+                return convT_stack(gy, w, None, add=add)
             if k == "fwd16" and FWD16_DX_ADD:  # copied only for the kernels that need it contiguous)
                 return conv_fwd16_dgrad(gy, w, add)
             if k == "convT64" and CONVT_DX_ADD:
@@ -747,6 +842,8 @@ class Route:
             return conv_s2_fewin(gy, s2_pairs(w), None, w.shape[0])
         if k == "convT64":
             return convT_mfma(gy if gy.data_ptr() % 16 == 0 else gy.clone(), w, None)
+        if k == "convTs":
+            return convT_stack(gy, w, None)
         if k == "gemm":
             return gemm_dgrad(gy, w, self.stride[0], self.transposed)
         gx, _, _ = torch.ops.aten.convolution_backward(

@@ -173,7 +173,8 @@ class _StackedUnitFn(torch.autograd.Function):
                                     dx_out=dy2[:, :c])
         up = ctx.skip_in
         gu = up.get("g") if up is not None else None
-        if n[0] and gu is not None and _conv.CONVT_DX_ADD and r_st.dx == "convT64" and gu.shape == x.shape:
+        if n[0] and gu is not None and gu.shape == x.shape and \
+                ((_conv.CONVT_DX_ADD and r_st.dx == "convT64") or (_conv.CONVT_STACK_DX_ADD and r_st.dx == "convTs")):
             # x is a stacked unit's output and its skip share gu is waiting: the kernel writes dX + gu into
             # channels [cu, 2 cu) of that unit's stacked output-gradient buffer, which that unit's backward
             # takes over when this very slice comes back to it as its output gradient (no add pass, no copy)
